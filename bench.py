@@ -19,6 +19,12 @@ The timed window holds the work the metric names:
 --mode env times the env kernels alone under a device-RNG random policy.
 
 Run: python bench.py [--gpus N --steps K --warmup W --config 2v2 --envs N_per_gpu]
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what takes runs of its own after the timed window: the CPU
+baseline (the C oracle's legs, cpu_baseline) and the measured HBM traffic of
+the roofline (two rocprofv3 child runs, live_traffic); --no-cpu-baseline and
+--no-live-traffic drop either one from a --full run.
+--dump-outputs DIR writes what the window's last step computed (dump_outputs).
 --gpus N > 1 without a torch.distributed launcher: bench.py starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
 process (before touching the GPU), relays rank 0's JSON line and exits with
@@ -140,9 +146,9 @@ def live_traffic(args, n, timeout_s=240):
     for a in sys.argv[1:]:  # (--lib passed on absolute: the children run in a scratch directory)
         if skip:
             skip = False
-        elif a == '--lib':
+        elif a in ('--lib', '--dump-outputs'):
             skip = True
-        elif a != '--cpu-all-cores' and not a.startswith('--lib='):
+        elif a not in ('--cpu-all-cores', '--full') and not a.startswith(('--lib=', '--dump-outputs=')):
             child.append(a)
     if args.lib:
         child += ['--lib', args.lib]
@@ -178,6 +184,52 @@ def live_traffic(args, n, timeout_s=240):
                               'write_counted_over_known': kw}
         res['traffic_bytes_per_step_calibrated'] = fetch / kf + write / kw
     return res
+
+
+DUMP_ENVS = 4096  # envs whose rows --dump-outputs keeps (a fixed, seeded sample of the rank's envs)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, env, n, tr=None, last=None):
+    """--dump-outputs DIR: the arrays the timed path handed its caller in the
+    window's last step, as DIR/<name>.npy (float32; rank 0's envs), so that two
+    builds run with the same arguments compare output for output (the env
+    seeds, the policy's seed and the sampling keys are fixed by the arguments).
+    Per-env arrays keep the rows of min(n, DUMP_ENVS) envs, drawn once with
+    numpy's default_rng(0) and sorted.
+      ppo mode -- the window ends on a horizon boundary, so its last step is
+      rollout step horizon - 1 and the GAE + PPO update after it: that step's
+      actions / logp / values (the policy kernel), rewards / dones / next_obs
+      (the env step; next_obs are the policy-input rows, bf16-rounded on the
+      mas_step_x path), the bootstrap values, the rollout's advantages and
+      returns [horizon, envs, agents] (GAE, normalised), the policy's
+      parameters after the update (one flat vector, in parameters() order)
+      and the update's last_stats (loss, pg, v, entropy, clipfrac);
+      env mode -- the last step's actions, obs, rewards and dones."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_ENVS), replace=False))
+    sel = torch.as_tensor(idx, device=env.device)
+    if tr is not None:
+        b, t = tr.buf, tr.cfg.horizon - 1
+        if tr.x_obs:
+            nxt = b.xb[t + 1].view(b.N, b.A, -1)[sel][..., :b.D]
+        else:
+            nxt = b.obs[t + 1][sel]
+        out = {'actions': b.actions[t][sel], 'logp': b.logp[t][sel], 'values': b.values[t][sel],
+               'rewards': b.rewards[t][sel], 'dones': b.dones[t][sel], 'next_obs': nxt,
+               'bootstrap_values': b.values[t + 1][sel], 'advantages': b.adv[:, sel], 'returns': b.ret[:, sel],
+               'policy_params': torch.cat([p.detach().reshape(-1) for p in tr.policy.parameters()]),
+               'update_stats': torch.stack([tr.last_stats[k].reshape(()) for k in
+                                            ('loss', 'pg', 'v', 'entropy', 'clipfrac') if k in tr.last_stats])}
+    else:
+        acts, (obs, rew, done, _) = last
+        out = {'actions': acts[sel], 'obs': obs[sel], 'rewards': rew[sel], 'dones': done[sel]}
+    out = {k: v.to(torch.float32).cpu().numpy() for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for k, v in out.items():
+        np.save(os.path.join(path, k + '.npy'), v)
 
 
 def free_port():
@@ -220,13 +272,19 @@ def parse_args():
     ap.add_argument('--horizon', type=int, default=None,
                     help='PPO rollout horizon; default: --steps when it is at most 64 (the timed window is then '
                          'exactly one PPO iteration), else 64')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed window also run the CPU baseline (cpu_baseline) and the rocprofv3 PMC child '
+                         'runs that measure roofline.traffic (live_traffic); off: the result line alone')
+    ap.add_argument('--dump-outputs', default=None, type=os.path.abspath, metavar='DIR',
+                    help='after the timed steps write what the last one computed as DIR/<name>.npy (dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-all-cores', action='store_true',
-                    help='add the CPU-baseline leg on every CPU this process may use (cpu_baseline leg iv)')
+                    help='with --full: add the CPU-baseline leg on every CPU this process may use (cpu_baseline leg iv)')
     ap.add_argument('--lib', default=None, type=os.path.abspath,
                     help='alternative libmas*.so (A/B variants; made absolute: the PMC child runs start elsewhere)')
     ap.add_argument('--no-live-traffic', action='store_true',
-                    help='skip the two rocprofv3 PMC child runs that measure roofline.traffic (live_traffic)')
+                    help='with --full: skip the two rocprofv3 PMC child runs that measure roofline.traffic '
+                         '(live_traffic)')
     ap.add_argument('--flush-stats', action='store_true',
                     help='end with one mas_flush_stats (the PMC child runs: the counters\' calibration kernel)')
     ap.add_argument('--shards', type=int, default=1,
@@ -402,11 +460,12 @@ def main():
         gen = torch.Generator(device=dev)
         gen.manual_seed(1234 + rank)
         acts = torch.empty((n, A, 6), dtype=torch.int8, device=dev)
+        state = {'last': None}  # what the last env.step returned (--dump-outputs)
 
         def one_step():
             u = torch.rand((n, A, 6), generator=gen, device=dev)
             acts.copy_((u * hi).to(torch.int8))
-            env.step(acts)
+            state['last'] = env.step(acts)
         preroll = 128 if args.preroll is None else args.preroll
         align = 0
         for _ in range(preroll + args.warmup):
@@ -437,6 +496,12 @@ def main():
         t = torch.tensor([dt, kern_ms, roll_ms, upd_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, kern_ms, roll_ms, upd_ms = (float(x) for x in t)
+    if args.dump_outputs and rank == 0:
+        if args.mode == 'ppo':
+            assert state['t'] == 0  # the window ended on a horizon boundary: its last step held the update
+            dump_outputs(args.dump_outputs, env, n, tr=tr)
+        else:
+            dump_outputs(args.dump_outputs, env, n, last=(acts, state['last']))
 
     diag = env.debug_counters()
     total_agent_steps = world * n * A * args.steps
@@ -492,7 +557,8 @@ def main():
     if args.flush_stats:
         env.flush_stats()
         torch.cuda.synchronize()
-    if rank == 0 and world == 1 and not args.no_live_traffic and os.environ.get('MAS_BENCH_CHILD') != '1':
+    if (args.full and rank == 0 and world == 1 and not args.no_live_traffic
+            and os.environ.get('MAS_BENCH_CHILD') != '1'):
         lt = live_traffic(args, n)
         line['roofline']['traffic_live'] = lt
         if 'traffic_bytes_per_step' in lt:
@@ -507,7 +573,7 @@ def main():
             line['roofline']['traffic_source'] = ('measured in this run: FETCH_SIZE + WRITE_SIZE per mas_step over '
                                                   'the timed window, two rocprofv3 --pmc child runs of this command, '
                                                   + how + '; raw counters in traffic_live')
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline(args.config, all_cores=args.cpu_all_cores)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -53,7 +53,7 @@ for step in "$@"; do
     smoke)
       cd $R && timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $? ;;
     bench)
-      cd $R && timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench_driver.log 2>&1 || exit $?
+      cd $R && timeout -k 10 400 python bench.py --steps 20 --warmup 5 --full > $O/bench_driver.log 2>&1 || exit $?
       cd $R && timeout -k 10 400 python bench.py --no-cpu-baseline --no-live-traffic > $O/bench.log 2>&1 || exit $? ;;
     benchcw0)
       # the PPO update on k_policy_train (MAS_POL_CW=0): the counted-wait kernel's A/B
@@ -168,7 +168,7 @@ for step in "$@"; do
       # trafab:<lib>[,<lib>...]: the driver window with its live FETCH / WRITE passes (roofline.traffic) per library
       for v in $(echo ${step#trafab:} | tr ',' ' '); do
         LIB=""; [ "$v" != main ] && LIB="--lib gym-ma-survival-2d_amd/masurvival/_lib/libmas_$v.so"
-        cd $R && timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline $LIB > $O/trafab_driver_$v.json 2>> $O/trafab.err || exit 1
+        cd $R && timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --full --no-cpu-baseline $LIB > $O/trafab_driver_$v.json 2>> $O/trafab.err || exit 1
       done ;;
     pmcenv)
       # FETCH_SIZE / WRITE_SIZE passes of the env-only workloads (2v2, FFA4 shard, 1v1, C4 / C5 full)
