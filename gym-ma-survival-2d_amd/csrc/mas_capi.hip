@@ -474,7 +474,6 @@ struct mas_handle {
     int* phys;  // the general-path list (k_pre -> general path, sharded) + [1] (unused) + [1] invalid-action count
                 // + [1] last count + [1] list guard, then the list's shard counts (Params::list_shards)
     uint8_t* gen_flag;  // [N] env left the fast path this step
-    float* sweep;       // A/B builds only (MAS_AB_KERNELS): k_gen_solve -> k_gen_toi
     mas_obs_layout layout;
     // the slow split (launch_step): side stream + fork / join events, made at
     // the first mas_step that splits, on the handle's device.  split: 0 the
@@ -728,11 +727,6 @@ int mas_create(const mas_config* cfg, int64_t n_envs, int32_t device, mas_handle
     const size_t phys_ints = shard_at + (size_t)kListShards * kShardStride;
     if (e == hipSuccess) e = hipMalloc(&h->phys, phys_ints * sizeof(int));
     if (e == hipSuccess) e = hipMemset(h->phys, 0, phys_ints * sizeof(int));
-    h->sweep = nullptr;
-#if MAS_AB_KERNELS
-    if (e == hipSuccess) e = hipMalloc(&h->sweep, (size_t)n_envs * 3 * kSweepAgents * sizeof(float));
-#endif
-    h->P.sweep = h->sweep;
     h->gen_flag = nullptr;
     if (e == hipSuccess) e = hipMalloc(&h->gen_flag, (size_t)n_envs);
     if (e == hipSuccess) e = hipMemset(h->gen_flag, 0, (size_t)n_envs);
@@ -777,7 +771,6 @@ int mas_create(const mas_config* cfg, int64_t n_envs, int32_t device, mas_handle
         e = hipHostGetDevicePointer((void**)&h->P.slow_sig, h->slow_sig, 0);
     }
     h->P.force_general = 0;
-    h->P.solve_one_lane = 0;
     h->P.toi_diag = nullptr;
 #ifdef MAS_PROFILE
     if (e == hipSuccess) e = hipMalloc(&h->P.prof, kProfWords * sizeof(unsigned long long));
@@ -799,7 +792,6 @@ int mas_destroy(mas_handle* h)
     if (h->seedbuf) (void)hipFree(h->seedbuf);
     if (h->P.prof) (void)hipFree(h->P.prof);
     if (h->phys) (void)hipFree(h->phys);
-    if (h->sweep) (void)hipFree(h->sweep);
     if (h->gen_flag) (void)hipFree(h->gen_flag);
     if (h->slow) (void)hipFree(h->slow);
     if (h->resetl) (void)hipFree(h->resetl);
@@ -1115,12 +1107,9 @@ int mas_debug_guards(mas_handle* h, int64_t* host_out)
 int mas_debug_force_general(mas_handle* h, int32_t on)
 {
     if (!h) return fail(MAS_ERR_INVALID_ARG, "mas_debug_force_general: null handle");
-#if !MAS_AB_KERNELS
-    if (on & 2) return fail(MAS_ERR_UNSUPPORTED, "mas_debug_force_general: the one-lane kernels are in libmas_ab.so only");
-#endif
+    if (on & 2) return fail(MAS_ERR_UNSUPPORTED, "mas_debug_force_general: bit 1 (the one-lane kernels) was removed");
     if (on & 4) return fail(MAS_ERR_INVALID_ARG, "mas_debug_force_general: bit 2 (the general split) was removed");
     h->P.force_general = (on & 1) ? 1 : 0;
-    h->P.solve_one_lane = (on & 2) ? 1 : 0;
     h->split = (on & 8) ? 0 : h->split_default;
     return MAS_OK;
 }

@@ -19,12 +19,6 @@
 #include "mas_math.h"
 #include "ziggurat_tables.h"
 
-// 1: test builds (make ab -> libmas_ab.so) with the one-lane general-path
-// kernels of mas_ab.h (scripts/ab_solve_golden.py); 0: the product library
-#ifndef MAS_AB_KERNELS
-#define MAS_AB_KERNELS 0
-#endif
-
 namespace mas {
 
 // damage causes (Health.causes values, semantics.py:490-500)
@@ -37,7 +31,6 @@ constexpr int kNumWalls = 4;
 constexpr int kMaxPhases = 9;   // zone radii incl. the appended 0
 constexpr int kStats = 19;      // MAS_STATS_WIDTH
 constexpr int kMaxLasers = 32;  // MAS_MAX_LASERS
-constexpr int kSweepAgents = 8;  // agents per env of the A/B builds' sweep buffer (mas_create)
 
 template <int AM_, int HM_, int BM_, int SM_, int KC_>
 struct Cap {
@@ -92,12 +85,12 @@ struct Params {
     int* phys_count;  // number of them: appended by k_pre, zeroed by the first post kernel on the caller's
                       // stream once the general path (its only reader) is done (graph-replay safe)
     // The general-path list in list_shards shards (kListShards, or 1): k_pre
-    // block b appends to shard xcd_block() / ceil(blocks / list_shards)
-    // (b % list_shards with MAS_XCD_SWZ=0) -- its entries at
-    // phys_list[shard * list_cap ..], its count at phys_count[shard *
-    // kShardStride] -- so that no single counter takes every wave's atomic
-    // (memory-side atomics on one address serialise: round 4's one counter
-    // cost k_pre ~17 us per wave in the PPO regime, profiles/r05e_prof_env_ppo.txt)
+    // block b appends to shard xcd_block() / ceil(blocks / list_shards) --
+    // its entries at phys_list[shard * list_cap ..], its count at
+    // phys_count[shard * kShardStride] -- so that no single counter takes
+    // every wave's atomic (memory-side atomics on one address serialise:
+    // round 4's one counter cost k_pre ~17 us per wave in the PPO regime,
+    // profiles/r05e_prof_env_ppo.txt)
     int list_shards, list_cap;
     int* phys_last;   // the last step's count, copied there before the zeroing (mas_debug_counters)
     int* list_overflow;  // appends to phys_list / slow_list / reset_list refused by their bounds (mas_debug_guards)
@@ -105,9 +98,7 @@ struct Params {
     int* reset_count;    // their count: zeroed by k_pre, appended by k_post_lanes, read by the reset launch
     int reset_in_post;   // the auto-reset runs inside k_post_lanes (no reset list, no reset launch)
     int force_general;   // test diagnostics (mas_debug_force_general): every env takes the general physics path
-    int solve_one_lane;  // A/B builds only (MAS_AB_KERNELS): the one-lane k_gen_solve + k_gen_toi
     uint8_t* gen_flag;  // [N] 1 = env e left the fast path this step (2: on the slow list)
-    float* sweep;     // A/B builds only: [env][3 * agent slots] b2Sweep c0.x, c0.y, a0 (k_gen_solve -> k_gen_toi)
     int* toi_diag;    // test diagnostics (mas_debug_set_toi_counter): per env, TOI events + 65536 per capped SolveTOI
     int* bad_actions; // env-steps whose actions fell outside MultiDiscrete([3,3,3,2,2,2]) (clamped; mas_invalid_actions)
     // the slow split (launch_step): envs whose last general-path step had a
@@ -228,30 +219,21 @@ __device__ __forceinline__ void wave_lds_sync()
 // XCDs (blocks b and b + 8 share one, MI355X_MICROARCH.md), so neighbouring
 // blocks sit on different L2s and each fetches the whole line.  The
 // bijective remap gives every group of XCD-mates one contiguous run of
-// blocks (cdna_hip_programming.md T1).  MAS_XCD_SWZ=0: the plain order.
-#ifndef MAS_XCD_SWZ
-#define MAS_XCD_SWZ 1
-#endif
+// blocks (cdna_hip_programming.md T1).
 __device__ __forceinline__ int64_t xcd_block()
 {
     const int64_t b = blockIdx.x;
-    if (!MAS_XCD_SWZ) return b;
     const int64_t nb = gridDim.x, q = nb / 8, r = nb % 8, x = b % 8;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
-// the general-path list in XCD-aware order too: contiguous k_pre shards,
-// the general kernel in runs of 16 waves (MAS_LIST_XCD=0: round 6's r06p order)
-#ifndef MAS_LIST_XCD
-#define MAS_LIST_XCD 1
-#endif
 // the same in runs of K consecutive blocks per XCD, dealt round-robin (a
 // grid whose first blocks alone have work -- the general kernel over its
-// list -- keeps every XCD busy); the last nb % 8K blocks keep their order
+// list of contiguous k_pre shards, in runs of 16 waves -- keeps every XCD
+// busy); the last nb % 8K blocks keep their order
 template <int K>
 __device__ __forceinline__ int64_t xcd_block_run()
 {
     const int64_t b = blockIdx.x;
-    if (!MAS_XCD_SWZ || !MAS_LIST_XCD) return b;
     const int64_t nb = gridDim.x, full = nb - nb % (8 * K);
     if (b >= full) return b;
     const int64_t x = b % 8, i = b / 8;

@@ -1,10 +1,9 @@
 // mas_gensolve.h -- b2World::Step Collide + island Solve of the general
 // physics path on a lane group per env (k_gen_solve_g, mas_kernels.inc).
 //
-// Same state changes, bit for bit, as world_step_solve (mas_ab.h, test builds) --
-// the one-lane-per-env form this replaces, itself the restatement of
-// b2World::Step up to SolveTOI (Box2D 2.3.x b2World::Solve, b2Island::Solve,
-// b2ContactSolver) that oracle/mas_oracle.c pins:
+// Same state changes, bit for bit, as ora_world_step (oracle/mas_oracle.c), the
+// C restatement of b2World::Step (Box2D 2.3.x b2World::Solve,
+// b2Island::Solve, b2ContactSolver, SolveTOI) that the tests compare against:
 //
 //   Collide   agent-agent pairs: few and order-dependent (a wake makes a
 //             later pair of the same agent eligible), so every lane of the
@@ -30,9 +29,8 @@
 //             (same_bits, mas_physics.h), per island.
 //
 // A group is G lanes (G >= statics, agent pairs and agents), 64 / G envs per
-// wave, over the compacted general-path list: where the one-lane kernel ran
-// every flagged env's serial Collide (A x (B + 4) pairs) and whole-env solve
-// on one lane, a wave here waits for its slowest island.
+// wave, over the compacted general-path list: a wave waits for its slowest
+// island.
 #pragma once
 
 #include "mas_step.h"
@@ -87,7 +85,7 @@ __device__ __forceinline__ uint32_t group_or(uint32_t v)
 }
 
 // static s's body (walls 0..3 from P, box s-4 from its state words) and its
-// world AABB (world_step_solve's cull)
+// world AABB (Collide's cull)
 template <class C>
 __device__ __forceinline__ void group_static(const Params& P, const uint32_t* __restrict__ state, int64_t N, int64_t e,
                                              bool load, int s, StaticG& g, V2& lo, V2& hi, float& bhx, float& bhy,
@@ -145,7 +143,7 @@ __device__ __forceinline__ void group_static(const Params& P, const uint32_t* __
 // iterations (exact fixed-point exit), impulse store, integration, <= 10
 // position iterations with the island's early exit, sleep.  The same
 // operations in the same order as the LDS loops of gen_solve_group (and as
-// world_solve, mas_ab.h).  new_awake: the members still awake.
+// world_solve, oracle/mas_oracle.c).  new_awake: the members still awake.
 template <class C, class KT>
 __device__ __forceinline__ void island_solve_regs(const Params& P, const SolveRec<C>& R, const KT& K,
                                                   const int (&qi)[SolveShape<C>::KR], int n, uint32_t members, V2 (&c)[C::AM],
@@ -289,15 +287,11 @@ __device__ __forceinline__ void island_solve_regs(const Params& P, const SolveRe
     }
 }
 
-// MAS_ISLAND_K=0: every multi-body island through island_solve_regs (A/B).
-// On for the classes with few statics only: the FFA classes' general kernel
+// For the classes with few statics only: the FFA classes' general kernel
 // went 245 -> 256 VGPRs with it and measured 1.2 % slower (r06s), the 2v2
 // class's 2 % faster
-#ifndef MAS_ISLAND_K
-#define MAS_ISLAND_K 1
-#endif
 template <class C>
-constexpr bool kIslandK = MAS_ISLAND_K && C::AM > 2 && C::NS <= 8;
+constexpr bool kIslandK = C::AM > 2 && C::NS <= 8;
 // island_solve_regs for an island of exactly NB (2 or 3) bodies: the members
 // are gathered into NB compact slots (ascending agent index) and every
 // contact's bodies re-indexed into them once, so each contact step selects
@@ -600,16 +594,10 @@ __device__ __forceinline__ void island_solve_one(const Params& P, const SolveRec
 // One world step's Collide + Solve of env e on this lane's group (lane s of
 // the group).  valid: the group holds an env (every lane of the wave runs the
 // ballots and the barrier).  rec: this workgroup's contact records.
-// TOI: also run b2World::SolveTOI of the step on the group (toi_agent_group,
-// mas_physics.h: lane s owns static s) -- the fused general path, one launch
-// per world step, no sweep buffer; else the sweep starts go to P.sweep for
-// k_gen_toi.
-// 1 (default): the SolveTOI agent loop runs by rank (each group's k-th TOI
-// agent in round k); 0: by agent index
-#ifndef MAS_TOI_BY_RANK
-#define MAS_TOI_BY_RANK 1
-#endif
-template <class C, bool TOI>
+// b2World::SolveTOI of the step runs on the group too (toi_agent_group,
+// mas_physics.h: lane s owns static s), its agent loop by rank (each group's
+// k-th TOI agent in round k).
+template <class C>
 __device__ __forceinline__ void gen_solve_group(const Params& P, uint32_t* __restrict__ state, int64_t N, int64_t e,
                                                 bool valid, int s, float* rec_lds, int slot, int pf = 0)
 {
@@ -1050,121 +1038,101 @@ __device__ __forceinline__ void gen_solve_group(const Params& P, uint32_t* __res
             }
         }
         }  // more than KC island contacts
-        if (!TOI) {
-            // the island's bodies (b2Island::Solve writes back every member)
-#pragma unroll
-            for (int j = 0; j < AM; ++j) {
-                if (!bit(members, j)) continue;
-                const float out[7] = {c[j].x, c[j].y, a[j], v[j].x, v[j].y, w[j], sl[j]};
-#pragma unroll
-                for (int q = 0; q < 7; ++q) state[state_index(7 * j + q, e, N)] = __float_as_uint(out[q]);
-            }
-        }
     }
     MAS_PROF(P, pf + kPfSolve);
     const uint32_t awake_fin = (awake_pre & ~solved) | group_or<G>(new_awake);
     uint32_t toi_ran = 0;
     int toi_events = 0;  // TOI events of the env's agents, + 65536 per capped agent
-    if (TOI) {
-        // every lane takes the solved bodies from its island's root lane
-        const int base = (int)(threadIdx.x & 63) & ~(G - 1);
+    // every lane takes the solved bodies from its island's root lane
+    const int base = (int)(threadIdx.x & 63) & ~(G - 1);
 #pragma unroll
-        for (int j = 0; j < AM; ++j) {
-            if (!bit(solved, j)) continue;
-            const int src = base + label[j];
-            c[j] = mk(__shfl(c[j].x, src, 64), __shfl(c[j].y, src, 64));
-            a[j] = __shfl(a[j], src, 64);
-            v[j] = mk(__shfl(v[j].x, src, 64), __shfl(v[j].y, src, 64));
-            w[j] = __shfl(w[j], src, 64);
-            sl[j] = __shfl(sl[j], src, 64);
-        }
-        // the island solve's impulse stores are ordered before SolveTOI's
-        // impulse resets (the same words, other lanes of this wave)
-        __threadfence_block();
-        MAS_PROF(P, pf + 5);  // the bodies' shuffles + the fence's wait for the impulse stores
-        // ---------------- b2World::SolveTOI, agent by agent on the group ----------------
-        // (TOI events of different agents are independent: statics never
-        // move, agent-agent pairs are not TOI pairs.)  An agent whose sweep
-        // every static's conservative pre-test rejects has no event and
-        // SolveTOI changes nothing for it (toi_agent_group's first pass):
-        // skipped.
-        // the agents this env's SolveTOI runs (the group agrees on the mask)
-        uint32_t need = 0;
+    for (int j = 0; j < AM; ++j) {
+        if (!bit(solved, j)) continue;
+        const int src = base + label[j];
+        c[j] = mk(__shfl(c[j].x, src, 64), __shfl(c[j].y, src, 64));
+        a[j] = __shfl(a[j], src, 64);
+        v[j] = mk(__shfl(v[j].x, src, 64), __shfl(v[j].y, src, 64));
+        w[j] = __shfl(w[j], src, 64);
+        sl[j] = __shfl(sl[j], src, 64);
+    }
+    // the island solve's impulse stores are ordered before SolveTOI's
+    // impulse resets (the same words, other lanes of this wave)
+    __threadfence_block();
+    MAS_PROF(P, pf + 5);  // the bodies' shuffles + the fence's wait for the impulse stores
+    // ---------------- b2World::SolveTOI, agent by agent on the group ----------------
+    // (TOI events of different agents are independent: statics never
+    // move, agent-agent pairs are not TOI pairs.)  An agent whose sweep
+    // every static's conservative pre-test rejects has no event and
+    // SolveTOI changes nothing for it (toi_agent_group's first pass):
+    // skipped.
+    // the agents this env's SolveTOI runs (the group agrees on the mask)
+    uint32_t need = 0;
 #pragma unroll
-        for (int i = 0; i < AM; ++i) {
-            const bool act = valid && bit(alive, i) && bit(awake_fin, i);
-            const bool keep = act && s < ns && !toi_reject(g, cs[i], c[i], P.agent_r);
-            if (group_ballot<G>(keep) != 0u) need |= 1u << i;
-        }
-#if MAS_TOI_BY_RANK
-        // Round k runs each group's k-th such agent (ascending index, the
-        // serial order per env), so a wave runs as many rounds as its busiest
-        // env has TOI agents; by agent index, agent i's round ran whenever
-        // any env of the wave needed agent i (up to AM rounds for one agent
-        // per env).  Agents' SolveTOI are independent (statics never move).
+    for (int i = 0; i < AM; ++i) {
+        const bool act = valid && bit(alive, i) && bit(awake_fin, i);
+        const bool keep = act && s < ns && !toi_reject(g, cs[i], c[i], P.agent_r);
+        if (group_ballot<G>(keep) != 0u) need |= 1u << i;
+    }
+    // Round k runs each group's k-th such agent (ascending index, the
+    // serial order per env), so a wave runs as many rounds as its busiest
+    // env has TOI agents; by agent index, agent i's round ran whenever
+    // any env of the wave needed agent i (up to AM rounds for one agent
+    // per env).  Agents' SolveTOI are independent (statics never move).
 #pragma unroll 1
-        for (int k = 0; k < AM; ++k) {
-            if (!__any(need != 0u)) break;
-            if (need == 0u) continue;
-            const int i = __builtin_ctz(need);
-            need &= need - 1u;
-            const V2 ci = sel(c, i), vi = sel(v, i);
-            const float ai = sel(a, i), wi = sel(w, i);
-#else
+    for (int k = 0; k < AM; ++k) {
+        if (!__any(need != 0u)) break;
+        if (need == 0u) continue;
+        const int i = __builtin_ctz(need);
+        need &= need - 1u;
+        const V2 ci = sel(c, i), vi = sel(v, i);
+        const float ai = sel(a, i), wi = sel(w, i);
+        EnvL<C> L;
+        L.alive_m = alive;
+        L.awake_m = awake_fin;
+        L.nbox = nbox;
 #pragma unroll
-        for (int i = 0; i < AM; ++i) {
-            if (!bit(need, i)) continue;
-            const V2 ci = c[i], vi = v[i];
-            const float ai = a[i], wi = w[i];
-#endif
-            EnvL<C> L;
-            L.alive_m = alive;
-            L.awake_m = awake_fin;
-            L.nbox = nbox;
-#pragma unroll
-            for (int k2 = 0; k2 < AM; ++k2) {
-                L.c[k2] = ci;
-                L.a[k2] = ai;
-                L.v[k2] = vi;
-                L.w[k2] = wi;
-            }
-#pragma unroll
-            for (int k2 = 0; k2 < C::BM; ++k2) {
-                L.bp[k2] = g.p;
-                L.bhx[k2] = bhx;
-                L.bhy[k2] = bhy;
-                L.bmeta[k2] = bmeta;
-            }
-            const uint32_t asti = sel(ast, i);
-            const ToiGroupOut o = toi_agent_group<C, G>(L, P, K, i, s, sel(cs, i), sel(as_, i), asti, dt);
-            toi_events += o.events;
-            put(c, i, o.c);
-            put(a, i, o.a);
-            put(v, i, o.v);
-            put(w, i, o.w);
-            const uint32_t keepm = ~((ns >= 32) ? 0xffffffffu : ((1u << ns) - 1u));
-            put(ast, i, (asti & keepm) | o.touch);
-            toi_ran |= 1u << i;
-            if (P.toi_diag && o.events && s == 0 && valid) atomicAdd(P.toi_diag + e, o.events);
+        for (int k2 = 0; k2 < AM; ++k2) {
+            L.c[k2] = ci;
+            L.a[k2] = ai;
+            L.v[k2] = vi;
+            L.w[k2] = wi;
         }
-        MAS_PROF(P, pf + kPfToi);
-        // a slow env (sub-step cap, or many events) takes the slow list next
-        // step (k_pre); the flag was cleared by this step's k_pre
-        if (valid && s == 0 && P.slow_k > 0 && ((toi_events >> 16) != 0 || (toi_events & 0xffff) >= P.slow_k)) {
-            P.slow_flag[e] = 1;
-            // tell the host (mapped memory; a vector store): it turns the slow split on
-            if (P.slow_sig) __hip_atomic_store(P.slow_sig, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+        for (int k2 = 0; k2 < C::BM; ++k2) {
+            L.bp[k2] = g.p;
+            L.bhx[k2] = bhx;
+            L.bhy[k2] = bhy;
+            L.bmeta[k2] = bmeta;
         }
+        const uint32_t asti = sel(ast, i);
+        const ToiGroupOut o = toi_agent_group<C, G>(L, P, K, i, s, sel(cs, i), sel(as_, i), asti, dt);
+        toi_events += o.events;
+        put(c, i, o.c);
+        put(a, i, o.a);
+        put(v, i, o.v);
+        put(w, i, o.w);
+        const uint32_t keepm = ~((ns >= 32) ? 0xffffffffu : ((1u << ns) - 1u));
+        put(ast, i, (asti & keepm) | o.touch);
+        toi_ran |= 1u << i;
+        if (P.toi_diag && o.events && s == 0 && valid) atomicAdd(P.toi_diag + e, o.events);
+    }
+    MAS_PROF(P, pf + kPfToi);
+    // a slow env (sub-step cap, or many events) takes the slow list next
+    // step (k_pre); the flag was cleared by this step's k_pre
+    if (valid && s == 0 && P.slow_k > 0 && ((toi_events >> 16) != 0 || (toi_events & 0xffff) >= P.slow_k)) {
+        P.slow_flag[e] = 1;
+        // tell the host (mapped memory; a vector store): it turns the slow split on
+        if (P.slow_sig) __hip_atomic_store(P.slow_sig, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (!valid) return;
-    if (TOI && s < AM && ((solved | toi_ran) >> s & 1u)) {
+    if (s < AM && ((solved | toi_ran) >> s & 1u)) {
         // agent s's body after the island solve and its SolveTOI
         const V2 cc = sel(c, s), vv = sel(v, s);
         const float out[7] = {cc.x, cc.y, sel(a, s), vv.x, vv.y, sel(w, s), sel(sl, s)};
 #pragma unroll
         for (int q = 0; q < 7; ++q) state[state_index(7 * s + q, e, N)] = __float_as_uint(out[q]);
     }
-    // touching words, awake mask, b2World's previous 1/dt, the sweep starts
+    // touching words, awake mask, b2World's previous 1/dt
     if (s == 0) {
         if (aat != aat0) K.set_aat(aat);
 #pragma unroll
@@ -1173,15 +1141,8 @@ __device__ __forceinline__ void gen_solve_group(const Params& P, uint32_t* __res
         state[state_index(TW::awake, e, N)] = awake_fin;
         state[state_index(P.w_invdt, e, N)] = __float_as_uint(inv_dt);
     }
-    // agents woken by Collide that no island holds cannot exist (a woken agent
-    // is alive and awake, so its island is solved); the sweep of agent s
-    if (!TOI && s < AM) {
-        float* sw = P.sweep + e * (3 * AM) + 3 * s;
-        const V2 c0s = sel(cs, s);
-        sw[0] = c0s.x;
-        sw[1] = c0s.y;
-        sw[2] = sel(as_, s);
-    }
+    // (agents woken by Collide that no island holds cannot exist: a woken
+    // agent is alive and awake, so its island is solved)
     MAS_PROF(P, pf + kPfStore);
 }
 

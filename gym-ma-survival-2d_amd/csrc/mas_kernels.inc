@@ -19,15 +19,11 @@
 // LDS.
 // Build flags (Makefile): -O3 -ffp-contract=off, IEEE f32 div/sqrt (hipcc
 // default), -mllvm -pragma-unroll-threshold so every per-body loop unrolls and
-// the env state stays in registers.  MAS_AB_KERNELS=1 (make ab, test builds
-// only) adds the one-lane general-path kernels of mas_ab.h.
+// the env state stays in registers.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "mas_lanes.h"
-#if MAS_AB_KERNELS
-#include "mas_ab.h"
-#endif
 
 namespace mas {
 
@@ -210,106 +206,14 @@ MAS_KERNEL_OCC(kSolveOcc<C>) void k_gen_solve_g(Params P, uint32_t* __restrict__
     // ws = -1: both world steps in this launch.  The second reloads what the
     // first stored, by other lanes of this wave: a workgroup-scope fence (the
     // wave is the workgroup) orders those stores before its loads
-    gen_solve_group<C, true>(P, state, N, e, valid, s, rec, slot, 0);
+    gen_solve_group<C>(P, state, N, e, valid, s, rec, slot, 0);
     if (ws < 0) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         MAS_PROF(P, 7);  // the fence's wait for the first world step's stores
-        gen_solve_group<C, true>(P, state, N, e, valid, s, rec, slot, 8);
+        gen_solve_group<C>(P, state, N, e, valid, s, rec, slot, 8);
     }
     MAS_PROF_FLUSH(P, P.gen_sparse ? 4 : 0, 0);
 }
-
-#if MAS_AB_KERNELS
-// TEST BUILDS ONLY (libmas_ab.so): the one-lane general path the lane-group
-// kernel replaced, for scripts/ab_solve_golden.py.  Per world step:
-// k_gen_solve (one lane per env over the full grid: Collide + island Solve)
-// then k_gen_toi (a lane group per (env, agent): SolveTOI).
-template <class C>
-MAS_KERNEL void k_gen_solve(Params P, uint32_t* __restrict__ state, int64_t N, int ws)
-{
-    const int64_t e = (int64_t)blockIdx.x * kWG + threadIdx.x;
-    if (e >= N || !P.gen_flag[e]) return;
-    EnvL<C> L;
-    Loader ld{state, N, e, 0};
-    visit_state(L, ld, kGDyn | kGBox);
-    const Cont<C, ContGlbStore<C>> K{{state, N, e, P.w_cont}};
-    StepScratch<C> S;
-    world_step_solve(L, P, K, (float)(1.0 / 60.0), S);
-    float* sw = P.sweep + e * (3 * C::AM);
-#pragma unroll
-    for (int i = 0; i < C::AM; ++i) {
-        sw[3 * i] = S.c0[i].x;
-        sw[3 * i + 1] = S.c0[i].y;
-        sw[3 * i + 2] = S.a0[i];
-    }
-    Storer st{state, N, e, 0};
-    visit_state(L, st, kGDyn);
-}
-
-template <class C>
-constexpr int kToiOcc = 2;
-template <class C>
-MAS_KERNEL_OCC(kToiOcc<C>) void k_gen_toi(Params P, uint32_t* __restrict__ state, int64_t N, int ws)
-{
-    static_assert(C::AM <= kSweepAgents, "the sweep buffer holds kSweepAgents agents per env (mas_create)");
-    constexpr int G = kToiG<C>;
-    const int64_t grp = ((int64_t)blockIdx.x * kWG + threadIdx.x) / G;
-    const int s = (int)(threadIdx.x & (G - 1));
-    const int64_t k = grp / C::AM;
-    const int i = (int)(grp - k * C::AM);
-    if (k >= min((int64_t)*P.phys_count, N)) return;
-    const int64_t e = P.phys_list[k];
-    // the words SolveTOI of agent i reads on lane s: the masks, nbox, agent
-    // i's pose and velocity, static s's box, put in every slot of L so the
-    // selects over them fold away
-    EnvL<C> L;
-    using TW = StateWords<C>;
-    L.alive_m = state[state_index(TW::alive, e, N)];
-    L.awake_m = state[state_index(TW::awake, e, N)];
-    if (!(bit(L.alive_m, i) && bit(L.awake_m, i))) return;
-    L.nbox = (int)state[state_index(TW::box, e, N)];
-    {
-        float d[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) d[q] = __uint_as_float(state[state_index(7 * i + q, e, N)]);
-        const int b = s < kNumWalls ? 0 : (s - kNumWalls < C::BM ? s - kNumWalls : C::BM - 1);
-        const int wb = TW::box + 1 + 6 * b;
-        const V2 bp = mk(__uint_as_float(state[state_index(wb, e, N)]), __uint_as_float(state[state_index(wb + 1, e, N)]));
-        const float bhx = __uint_as_float(state[state_index(wb + 2, e, N)]);
-        const float bhy = __uint_as_float(state[state_index(wb + 3, e, N)]);
-        const int bmeta = (int)state[state_index(wb + 4, e, N)];
-#pragma unroll
-        for (int k2 = 0; k2 < C::AM; ++k2) {
-            L.c[k2] = mk(d[0], d[1]);
-            L.a[k2] = d[2];
-            L.v[k2] = mk(d[3], d[4]);
-            L.w[k2] = d[5];
-        }
-#pragma unroll
-        for (int k2 = 0; k2 < C::BM; ++k2) {
-            L.bp[k2] = bp;
-            L.bhx[k2] = bhx;
-            L.bhy[k2] = bhy;
-            L.bmeta[k2] = bmeta;
-        }
-    }
-    const float* sw = P.sweep + e * (3 * C::AM);
-    const V2 c0 = mk(sw[3 * i], sw[3 * i + 1]);
-    const float a0 = sw[3 * i + 2];
-    const Cont<C, ContGlbStore<C>> KG{{state, N, e, P.w_cont}};
-    const uint32_t t0 = KG.ast(i);
-    const ToiGroupOut o = toi_agent_group<C, G>(L, P, KG, i, s, c0, a0, t0, (float)(1.0 / 60.0));
-    if (s != 0) return;
-    if (P.toi_diag && o.events) atomicAdd(P.toi_diag + e, o.events);
-    const uint32_t keep = ~((kNumWalls + L.nbox >= 32) ? 0xffffffffu : ((1u << (kNumWalls + L.nbox)) - 1u));
-    KG.set_ast(i, (t0 & keep) | o.touch);
-    // this agent only: c, a, v, w (dyn words 7 i + 0..5; SolveTOI never
-    // changes sleep time or the awake mask of an awake agent)
-    const float out[6] = {o.c.x, o.c.y, o.a, o.v.x, o.v.y, o.w};
-#pragma unroll
-    for (int q = 0; q < 6; ++q) state[state_index(7 * i + q, e, N)] = __float_as_uint(out[q]);
-}
-#endif
 
 // Env selection of the post-physics kernels (k_post_lanes, k_obs).
 // kAllEnvs: every env, one stream.  The slow split (launch_step)
@@ -706,10 +610,9 @@ void launch_post(dim3 g, hipStream_t s, const Params& P, uint32_t* st, int64_t N
 }
 
 // the general physics path of the envs k_pre flagged, on stream s: one
-// k_gen_solve_g for both world steps (MAS_GEN_FUSE2=0: one per world step;
-// A/B builds: k_gen_solve + k_gen_toi per world step when P.solve_one_lane)
+// k_gen_solve_g for both world steps (MAS_GEN_FUSE2=0: one per world step)
 template <class C>
-void launch_general(dim3 g, hipStream_t s, const Params& P, uint32_t* st, int64_t N)
+void launch_general(hipStream_t s, const Params& P, uint32_t* st, int64_t N)
 {
     const dim3 gs((unsigned)((N + SolveShape<C>::EPW - 1) / SolveShape<C>::EPW));
     // both world steps in one launch (a wave's envs run their second world
@@ -721,25 +624,11 @@ void launch_general(dim3 g, hipStream_t s, const Params& P, uint32_t* st, int64_
         const char* v = getenv("MAS_GEN_FUSE2");
         return !(v && v[0] == '0');
     }();
-#if MAS_AB_KERNELS
-    if (fuse2 && !P.solve_one_lane) {
-#else
     if (fuse2) {
-#endif
         hipLaunchKernelGGL((k_gen_solve_g<C>), gs, dim3(kWG), 0, s, P, st, N, -1);
         return;
     }
-    for (int k = 0; k < 2; ++k) {
-#if MAS_AB_KERNELS
-        if (P.solve_one_lane) {
-            const dim3 gt((unsigned)((N * C::AM * kToiG<C> + kWG - 1) / kWG));
-            hipLaunchKernelGGL(k_gen_solve<C>, g, dim3(kWG), 0, s, P, st, N, k);
-            hipLaunchKernelGGL(k_gen_toi<C>, gt, dim3(kWG), 0, s, P, st, N, k);
-            continue;
-        }
-#endif
-        hipLaunchKernelGGL((k_gen_solve_g<C>), gs, dim3(kWG), 0, s, P, st, N, k);
-    }
+    for (int k = 0; k < 2; ++k) hipLaunchKernelGGL((k_gen_solve_g<C>), gs, dim3(kWG), 0, s, P, st, N, k);
 }
 
 // mas_step.  The slow split (sp non-null): after k_pre the side stream runs
@@ -758,20 +647,18 @@ void launch_step(dim3 g, hipStream_t s, const Params& P0, uint32_t* st, int64_t 
     // list (k_obs with the reset in front when A == C::AM, else k_reset + k_obs)
     const bool rip = ar && reset_fits_post<C>(P0);
     const bool fuse = ar && !rip && kObsReset<C> && P0.A == C::AM && (kWG % P0.A) == 0;
-    // the one-lane A/B kernels walk every flagged env: one stream only
-    const bool split = sp && !P0.solve_one_lane && (!ar || fuse || rip);
+    const bool split = sp && (!ar || fuse || rip);
     // the slow list exists only in the slow split (elsewhere nothing would run it)
     Params P = P0;
     P.slow_route = split ? 1 : 0;
     P.reset_in_post = rip ? 1 : 0;
     // the general-path list's shards: each takes the appends of at most
     // ceil(blocks / shards) k_pre blocks (a contiguous run in the XCD-aware
-    // order, mas_lanes.h), so at most their envs (the one-lane A/B kernels
-    // read one list)
+    // order, mas_lanes.h), so at most their envs
     {
         const int64_t nblk = (N + kWG / C::AM - 1) / (kWG / C::AM);
         const int64_t cap = (nblk + kListShards - 1) / kListShards * (kWG / C::AM);
-        const bool sharded = !P0.solve_one_lane && cap * kListShards <= N + kListSlack;
+        const bool sharded = cap * kListShards <= N + kListSlack;
         P.list_shards = sharded ? kListShards : 1;
         P.list_cap = sharded ? (int)cap : (int)N;
     }
@@ -787,14 +674,14 @@ void launch_step(dim3 g, hipStream_t s, const Params& P0, uint32_t* st, int64_t 
         Q.gen_sparse = 1;
         Q.reset_list = P.reset_list + N;  // the side stream's own auto-reset list (without the reset in place)
         Q.reset_count = P.reset_count + 1;
-        launch_general<C>(g, sp->side, Q, st, N);
+        launch_general<C>(sp->side, Q, st, N);
         launch_post<C, kGenEnvs>(g, sp->side, Q, st, N, ob, rw, dn, fuse, false);
-        launch_general<C>(g, s, P, st, N);
+        launch_general<C>(s, P, st, N);
         launch_post<C, kMainEnvs>(g, s, P, st, N, ob, rw, dn, fuse, false);
         (void)hipEventRecord(sp->join, sp->side);
         (void)hipStreamWaitEvent(s, sp->join, 0);
     } else {
-        launch_general<C>(g, s, P, st, N);
+        launch_general<C>(s, P, st, N);
         launch_post<C, kAllEnvs>(g, s, P, st, N, ob, rw, dn, fuse, ar && !fuse && !rip);
     }
     launch_lidar<C>(s, P, st, N, nullptr, ob);

@@ -645,8 +645,8 @@ MAS_HD bool toi_reject(const StaticG& g, V2 p0, V2 p1, float rB)
 }
 
 // ---------------------------------------------------------------------------
-// Lane-group b2World::SolveTOI (k_gen_toi): G lanes per (env, agent) and
-// lane s of the group owns static s (walls 0..3, then the boxes).  What is
+// Lane-group b2World::SolveTOI (toi_agent_group, called by gen_solve_group):
+// G lanes per (env, agent) and lane s of the group owns static s (walls 0..3, then the boxes).  What is
 // independent per static runs on its own lane -- the conservative pre-test
 // and b2TimeOfImpact against the agent's sweep, the narrowphase update of
 // each contact (b2Contact::Update) when the island is built -- and the

@@ -146,27 +146,12 @@ __global__ void k_pack(int D, int ks1, const float* __restrict__ W1, const float
     }
 }
 
-// timing experiments only (results garbage): 1 no tanh, 2 no sampling, 4 no MFMA, 8 no x loads
 #ifndef MAS_POL_OCC_ACT
 #define MAS_POL_OCC_ACT 2
 #endif
-#ifndef MAS_POL_EXP
-#define MAS_POL_EXP 0
-#endif
-// scheduling strategy hint for the MFMA + LDS-read loops (A/B builds)
-#ifndef MAS_POL_IGLP
-#define MAS_POL_IGLP -1
-#endif
-__device__ __forceinline__ void iglp()
-{
-#if MAS_POL_IGLP >= 0
-    __builtin_amdgcn_iglp_opt(MAS_POL_IGLP);
-#endif
-}
 
 __device__ __forceinline__ f16v mfma(bf8 a, bf8 b, f16v c)
 {
-    if (MAS_POL_EXP & 4) return c + (float)a[0];
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
@@ -177,7 +162,6 @@ __device__ __forceinline__ f16v mfma(bf8 a, bf8 b, f16v c)
 // (~1 ulp each for exp / rcp; the result is rounded to bf16 anyway).
 __device__ __forceinline__ float tanh_pre(float a, float bc)
 {
-    if (MAS_POL_EXP & 1) return a;
     const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(a, kTanhC, bc));
     return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
@@ -219,10 +203,6 @@ __device__ __forceinline__ bf8 x_frag_f32_full(const float* __restrict__ obs, in
 __device__ __forceinline__ bf8 x_frag_f32(const float* __restrict__ obs, int64_t row, bool ok, int D, int k0)
 {
     bf8 f;
-    if (MAS_POL_EXP & 8) {
-        for (int j = 0; j < 8; ++j) f[j] = (__bf16)(float)(row + k0 + j);
-        return f;
-    }
     const float* p = obs + row * D + k0;
     if (ok && (D & 3) == 0 && k0 + 8 <= D) {
         const float4 a = *reinterpret_cast<const float4*>(p);
@@ -273,19 +253,10 @@ struct Stage1 {
 };
 
 // The packed biases (b1p, b2p, b3: kBiasF floats) copied into LDS once per
-// workgroup (MAS_POL_LDSB=1): the per-M-tile bias reads of the layers become
-// ds_read_b128 instead of global loads.  No gain measured (r04g: the A/B
-// was within policy_bench's run-order bias -- the same train kernel timed
-// 3.88 vs 3.52 ms as first vs second library of one process): the MFMA
-// loops read a 1-KiB weight fragment from LDS per 32-cycle MFMA on every
-// SIMD, the CU's whole 128 B/clk, so LDS bias reads compete with the weight
-// reads, while the global bias loads the compiler issues early are mostly
-// hidden.  Off by default (k_policy_train_db always stages them: its
-// double-buffered layout has the room).  Ordered before every read by the
-// first weight stage's drain + barrier.
-#ifndef MAS_POL_LDSB
-#define MAS_POL_LDSB 0
-#endif
+// workgroup, for k_policy_train_db (its double-buffered layout has the
+// room); the other kernels read them from global memory (no gain measured
+// from LDS there, r04g).  Ordered before every read by the first weight
+// stage's drain + barrier.
 constexpr int kBiasF = 2 * kMT * 2 * 16 + kO;
 __device__ __forceinline__ const float* bias_lds(float* __restrict__ bl, const float* __restrict__ fb_b1)
 {
@@ -378,7 +349,6 @@ __device__ __forceinline__ f16v layers23(STG& S, const bf8* __restrict__ W23,
             const int mo = kMT / 2 * hf + q;
             f16v a = f16v{};
             const bf8* w = wl + q * 16 * 64 + l;
-            iglp();
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) a = mfma(w[kk * 64], h1[kk >> 1][kk & 1], a);
             float b[16];
@@ -513,12 +483,7 @@ __global__ __launch_bounds__(64 * kWaves, MAS_POL_OCC_ACT * 4 / kWaves) void k_p
     const Layout Lo{ks1};
     const bf8* F = reinterpret_cast<const bf8*>(packed);
     const float* FB = reinterpret_cast<const float*>(packed);
-#if MAS_POL_LDSB
-    __shared__ float bl[kBiasF];
-    const float* B1 = bias_lds(bl, FB + Lo.b1());
-#else
     const float* B1 = FB + Lo.b1();
-#endif
     const int l = threadIdx.x & 63, h = l >> 5;
     const int64_t row0 = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * 32;
     const bool on = row0 < M;  // wave-uniform
@@ -573,16 +538,10 @@ __global__ __launch_bounds__(64 * kWaves, MAS_POL_OCC_ACT * 4 / kWaves) void k_p
     const f16v z3 = layers23<false>(S, F + Lo.w23(), B1 + kMT * 2 * 16, l, on, h1, h2);  // last barrier
     if (!on) return;
     if constexpr (SPLIT) {
-        if (!(MAS_POL_EXP & 2)) {
-            act_sample_split(z3, B1 + 2 * kMT * 2 * 16, l, ok, row, seed, step, first_row, act, logp, value);
-            return;
-        }
-    }
-    if (h != 0 || !ok) return;
-    if (MAS_POL_EXP & 2) {
-        value[row] = z3[0] + z3[15];
+        act_sample_split(z3, B1 + 2 * kMT * 2 * 16, l, ok, row, seed, step, first_row, act, logp, value);
         return;
     }
+    if (h != 0 || !ok) return;
     float z[kO];
     const float* b3 = B1 + 2 * kMT * 2 * 16;
 #pragma unroll
@@ -1193,12 +1152,7 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
 {
     __shared__ bf8 wl[kLdsFrag];
     const float* FB = reinterpret_cast<const float*>(A.packed);
-#if MAS_POL_LDSB
-    __shared__ float bl[kBiasF];
-    const float* B1 = bias_lds(bl, FB + Layout{A.ks1}.b1());
-#else
     const float* B1 = FB + Layout{A.ks1}.b1();
-#endif
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float st[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if ((int64_t)(blockIdx.x + 1) * kTWaves * 32 <= A.M)  // block-uniform
@@ -1245,9 +1199,6 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
 // k_policy_train (policy_train).  Same operations in the same order per row:
 // bit-identical to k_policy_train (test_counted_wait_train_kernel_is_bit_identical).
 // ---------------------------------------------------------------------------
-#ifndef MAS_POL_DB_SB
-#define MAS_POL_DB_SB 1
-#endif
 constexpr int kDW = 8;                  // waves per workgroup
 constexpr int kDRows = 32 * kDW;        // rows per block
 constexpr int kDCopy = 64 * kDW;        // fragments one copy round moves (one per thread)
@@ -1320,9 +1271,7 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         // per-word store offsets stayed live from phase C to G and spilled)
         asm volatile("" : "+v"(row));
         store_rows2<OFF32>(base, LD, row, t, h, v);
-#if MAS_POL_DB_SB
         __builtin_amdgcn_sched_barrier(0);
-#endif
     };
     const int64_t b0 = blockIdx.x;
     // the prologue's copies land before the loop (the same order as landing

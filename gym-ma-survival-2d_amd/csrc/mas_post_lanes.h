@@ -29,13 +29,9 @@
 
 namespace mas {
 
-constexpr int kPostObsW = 32;  // obs column window of the LDS tile (MAS_POST_OBS_SEQ=0)
-// obs rows: 1 = each lane generates its own row once, in column order, and
+// obs rows: each lane generates its own row once, in column order, and
 // stores it with 16-B (8-B, 4-B when D is not a multiple of 4 / 2) stores
-// (write_obs_row_seq); 0 = column windows of an LDS tile (write_obs_row_v)
-#ifndef MAS_POST_OBS_SEQ
-#define MAS_POST_OBS_SEQ 1
-#endif
+// (write_obs_row_seq)
 
 template <class C>
 struct PostLds {
@@ -60,9 +56,6 @@ struct PostLds {
             uint32_t drop[kDropW * C::AM * S];  // [field][agent][slot]
             double ang[C::AM * C::SM * S];       // DeathDrop angles, [k][slot]
         } dd;
-#if !MAS_POST_OBS_SEQ
-        float tile[kWG * (kPostObsW + 1)];  // obs rows, one column window
-#endif
     } u;
 };
 
@@ -377,153 +370,10 @@ __device__ __forceinline__ void zone_tick_v(const PostV<C>& V, const Params& P)
 // The obs row of agent i of slot j (write_obs_row, mas_step.h) from LDS:
 // the agent table (post-step healths), the post-tick zone, the post-pickup
 // heals, boxes and box items and their seen bytes; own: the lane's
-// inventory's last item.  Sink: WinRow-like (column window).
-struct WinRowP {
-    float* p;
-    int c0;
-    __device__ void operator()(int k, float v)
-    {
-        const unsigned kk = (unsigned)(k - c0);
-        p[kk < (unsigned)kPostObsW ? kk : (unsigned)kPostObsW] = v;
-    }
-    __device__ bool want(int off, int len) const { return off < c0 + kPostObsW && off + len > c0; }
-};
-
-template <class C, class Sink>
-__device__ __forceinline__ void write_obs_row_v(const PostV<C>& V, const Params& P, uint32_t alive_m, int i,
-                                                int lastmeta, float lhx, float lhy, Sink& row)
-{
-    using PV = PostV<C>;
-    const int A = P.A, as_ = P.as_;
-    const bool alive = bit(alive_m, i);
-    const int pp = __popc(alive_m & ((1u << i) - 1u));  // post-despawn list position (quirk D1)
-    // agent + others rows (_fetch_agents_observations :659-704)
-    if (row.want(P.o_agent, as_) || row.want(P.o_oth, (A - 1) * as_) || row.want(P.o_othm, A - 1)) {
-        for (int k = 0; k < A; ++k) {
-            const bool ak = bit(alive_m, k);
-            const int ok = k < i ? k : k - 1;
-            int o = k == i ? P.o_agent : P.o_oth + ok * as_;
-            if (!row.want(o, as_) && !(k != i && row.want(P.o_othm + ok, 1))) continue;
-            row(o++, (float)k);
-            if (P.teams) row(o++, (float)team_of(P, k));
-            row(o++, ak ? V.ag(6, k) : 0.0f);
-#pragma unroll
-            for (int f = 0; f < 6; ++f) row(o++, ak ? V.ag(f, k) : 0.0f);
-            if (k != i) {
-                // others_mask: seen list at the post-despawn list index (quirk D1)
-                float m = 1.0f;
-                if (alive && ak && (V.sn(BIdx<C>::agent + k) >> pp) & 1u) m = 0.0f;
-                row(P.o_othm + ok, m);
-            }
-        }
-    }
-    if (row.want(P.o_zone, 6)) {
-        const int phase = (int)V.zw(PV::kZPhase);
-        row(P.o_zone + 0, __uint_as_float(V.zw(PV::kZPx)));
-        row(P.o_zone + 1, __uint_as_float(V.zw(PV::kZPy)));
-        row(P.o_zone + 2, __uint_as_float(V.zw(PV::kZRad)));
-        float z3 = 0.0f, z4 = 0.0f, z5 = 0.0f;
-        if (phase < P.zone_phases - 1) {
-            const V2 zn = V.zc(phase + 1);
-            z3 = zn.x;
-            z4 = zn.y;
-#pragma unroll
-            for (int k = 0; k < kMaxPhases; ++k)
-                if (k == phase + 1) z5 = opq(P.zradf[k]);
-        }
-        row(P.o_zone + 3, z3);
-        row(P.o_zone + 4, z4);
-        row(P.o_zone + 5, z5);
-    }
-    if (P.H > 0 && (row.want(P.o_heal, 2 * P.H) || row.want(P.o_healm, P.H))) {
-        const int nh = V.nheal();
-        for (int h = 0; h < P.H; ++h) {
-            if (!row.want(P.o_heal + 2 * h, 2) && !row.want(P.o_healm + h, 1)) continue;
-            const bool present = h < nh;
-            const V2 hp = V.hp(h);
-            row(P.o_heal + 2 * h, present ? hp.x : 0.0f);
-            row(P.o_heal + 2 * h + 1, present ? hp.y : 0.0f);
-            float m;
-            if (P.omniscient) m = present ? 0.0f : 1.0f;
-            else m = (present && alive && ((V.sn(BIdx<C>::heal + h) >> pp) & 1u)) ? 0.0f : 1.0f;
-            row(P.o_healm + h, m);
-        }
-    }
-    if (P.B > 0 && (row.want(P.o_box, 11 * P.B) || row.want(P.o_boxm, P.B))) {
-        const int nb = V.nbox();
-        for (int b = 0; b < P.B; ++b) {
-            const bool present = b < nb;
-            if (row.want(P.o_box + 11 * b, 11)) {
-                const int meta = V.bmeta(b);
-                const Poly4 poly = box_poly(V.bhx(b), V.bhy(b), box_rot(meta), box_copied(meta));
-                const V2 bp = V.bp(b);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    row(P.o_box + 11 * b + 2 * v, present ? poly.v[v].x : 0.0f);
-                    row(P.o_box + 11 * b + 2 * v + 1, present ? poly.v[v].y : 0.0f);
-                }
-                row(P.o_box + 11 * b + 8, present ? bp.x : 0.0f);
-                row(P.o_box + 11 * b + 9, present ? bp.y : 0.0f);
-                row(P.o_box + 11 * b + 10, 0.0f);  // box bodies always have angle 0
-            }
-            if (!row.want(P.o_boxm + b, 1)) continue;
-            float m;
-            if (P.omniscient) m = present ? 0.0f : 1.0f;
-            else m = (present && alive && ((V.sn(BIdx<C>::box + b) >> pp) & 1u)) ? 0.0f : 1.0f;
-            row(P.o_boxm + b, m);
-        }
-    }
-    if (P.B > 0 && (row.want(P.o_bi, 10 * P.B) || row.want(P.o_bim, P.B))) {
-        const int ni = V.nbi();
-        for (int b = 0; b < P.B; ++b) {
-            const bool present = b < ni;
-            if (row.want(P.o_bi + 10 * b, 10)) {
-                const float hx = V.ihx(b), hy = V.ihy(b);
-                const int rot = bi_rot(V.imeta(b));
-                const V2 ip = V.ip(b);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const V2 cv = box_corner(hx, hy, rot + v);
-                    row(P.o_bi + 10 * b + 2 * v, present ? cv.x : 0.0f);
-                    row(P.o_bi + 10 * b + 2 * v + 1, present ? cv.y : 0.0f);
-                }
-                row(P.o_bi + 10 * b + 8, present ? ip.x : 0.0f);
-                row(P.o_bi + 10 * b + 9, present ? ip.y : 0.0f);
-            }
-            if (!row.want(P.o_bim + b, 1)) continue;
-            float m;
-            if (P.omniscient) m = present ? 0.0f : 1.0f;
-            else m = (present && alive && ((V.sn(BIdx<C>::bitem + b) >> pp) & 1u)) ? 0.0f : 1.0f;
-            row(P.o_bim + b, m);
-        }
-    }
-    // lidars: zeros here; k_lidar writes the columns afterwards
-    if (P.n_lasers > 0 && row.want(P.o_lid, P.n_lasers)) {
-        for (int k = 0; k < P.n_lasers; ++k) row(P.o_lid + k, 0.0f);
-    }
-    // usable inventory slots (:620-654)
-    if (row.want(P.o_hs, 1) || row.want(P.o_hsm, 1) || row.want(P.o_bs, 8) || row.want(P.o_bsm, 1)) {
-        if (P.H > 0) {
-            const bool isheal = it_kind(lastmeta) == kItemHeal;
-            row(P.o_hs, isheal ? (float)P.healing : 0.0f);
-            row(P.o_hsm, isheal ? 0.0f : 1.0f);
-        }
-        if (P.B > 0) {
-            const bool isbox = it_kind(lastmeta) == kItemBox;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const V2 cv = box_corner(lhx, lhy, it_rot(lastmeta) + v);
-                row(P.o_bs + 2 * v, isbox ? cv.x : 0.0f);
-                row(P.o_bs + 2 * v + 1, isbox ? cv.y : 0.0f);
-            }
-            row(P.o_bsm, isbox ? 0.0f : 1.0f);
-        }
-    }
-}
-
+// inventory's last item.
 // A lane's obs row in column order (the layout of build_layout, mas_capi.hip:
 // the observation keys sorted by name), into a sink that packs consecutive
-// columns into 16-B stores.  Same values as write_obs_row_v.
+// columns into 16-B stores.
 struct SeqRow {
     float* p;   // the row
     int vm1;    // store width in floats - 1 (3, 1 or 0; wave-uniform)
@@ -1591,7 +1441,6 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
     wave_lds_sync();  // the agent table's healths and every LDS group are final
     const int D = P.D;
     const bool row_on = valid && i < A;
-#if MAS_POST_OBS_SEQ
     const uintptr_t ob = reinterpret_cast<uintptr_t>(obs);
     const bool ex = A == C::AM && P.B == C::BM && P.H == C::HM && P.n_lasers == 0;
     if (P.xrow) {
@@ -1622,46 +1471,6 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
         else if (ex) write_obs_row_seq<C, true, false>(V, P, alive_m, i, lastmeta, lhx, lhy, o);
         else write_obs_row_seq<C, false, false>(V, P, alive_m, i, lastmeta, lhx, lhy, o);
     }
-#else
-    const int trow = j * A + i;  // tile row (the wave's rows are consecutive unless kGenEnvs)
-    const int64_t r0 = M == kGenEnvs ? 0 : k0 * A;
-    const int64_t rr = e * A + i;  // this lane's obs row
-    const uint64_t act = __ballot(row_on);
-    float* row_tile = lds.u.tile + trow * (kPostObsW + 1);
-    for (int c0 = 0; c0 < D; c0 += kPostObsW) {
-        if (row_on) {
-            WinRowP sink{row_tile, c0};
-            write_obs_row_v(V, P, alive_m, i, lastmeta, lhx, lhy, sink);
-        }
-        wave_lds_sync();  // the tile's rows are in LDS
-        // lane = (row parity, column): each store instruction writes two
-        // 128-B row segments; 8 rows per lane per chunk, the LDS reads of a
-        // chunk issued before its stores
-        const int col = lane & (kPostObsW - 1), half = lane / kPostObsW;
-        const bool col_ok = c0 + col < D;
-        const int nrows = S * A;
-        for (int q0 = 0; q0 < nrows; q0 += 16) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int q = q0 + 2 * k + half;
-                v[k] = q < nrows ? lds.u.tile[q * (kPostObsW + 1) + col] : 0.0f;
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int q = q0 + 2 * k + half;
-                const int sq = q / A, aq = q - sq * A;  // tile row q: slot q / A, agent q % A
-                const bool on = q < nrows && ((act >> (sq * AM + aq)) & 1ull);
-                if (on && col_ok) {
-                    const int64_t orow = M == kGenEnvs ? lds.eidx[sq] * A + aq : r0 + q;
-                    obs[orow * D + c0 + col] = v[k];
-                }
-            }
-        }
-        wave_lds_sync();  // the tile's reads are done before the next window's rows
-    }
-    (void)rr;
-#endif
     MAS_PROF(P, 45);
     MAS_PROF_FLUSH(P, M == kGenEnvs ? 5 : 2, 41);
 }

@@ -200,12 +200,10 @@ class VecMaSurvival:
         check(self._lib.mas_debug_guards(self._h, out))
         return {'list_overflow': int(out[0])}
 
-    def force_general(self, on: bool = True, one_lane_solve: bool = False):
-        """Test diagnostics: every env takes the general physics path (on);
-        one_lane_solve (test library libmas_ab.so only): the general path runs
-        the one-lane k_gen_solve + k_gen_toi instead of k_gen_solve_g."""
+    def force_general(self, on: bool = True):
+        """Test diagnostics: every env takes the general physics path (on)."""
         bits = getattr(self, '_dbg_bits', 0) & 12
-        self._dbg_bits = bits | int(bool(on)) | (2 if one_lane_solve else 0)
+        self._dbg_bits = bits | int(bool(on))
         check(self._lib.mas_debug_force_general(self._h, self._dbg_bits))
 
     def split_step(self, mode=None):
@@ -213,7 +211,7 @@ class VecMaSurvival:
         0 the caller's stream alone, None the handle's default (the slow
         split, MAS_SPLIT)."""
         bits = {0: 8, None: 0}[mode]
-        self._dbg_bits = (getattr(self, '_dbg_bits', 0) & 3) | bits
+        self._dbg_bits = (getattr(self, '_dbg_bits', 0) & 1) | bits
         check(self._lib.mas_debug_force_general(self._h, self._dbg_bits))
 
     def invalid_actions(self, reset: bool = True) -> int:

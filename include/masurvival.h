@@ -335,9 +335,8 @@ int mas_debug_guards(mas_handle* h, int64_t* host_out);
 
 /* Test diagnostics: bit 0 of `on` sends every env of every following
  * mas_step through the general physics path (the contact-free fast path
- * gives up for all envs); bit 1 runs the general path one lane per env
- * (k_gen_solve + k_gen_toi) instead of on lane groups (k_gen_solve_g) -- only
- * in the test library libmas_ab.so (`make ab`), MAS_ERR_UNSUPPORTED here;
+ * gives up for all envs); bit 1 (the former one-lane-per-env general
+ * kernels, removed) is rejected with MAS_ERR_UNSUPPORTED and changes nothing;
  * bit 3 keeps mas_step on the caller's stream.  Default (MAS_SPLIT unset or
  * 2 in the environment at mas_create): the slow split, the envs whose last
  * general-path step had a SolveTOI at the sub-step cap (or >= MAS_SLOW_K,

@@ -2,8 +2,8 @@
 per-GPU shard sizes, bit-exact against the oracle.
 
 The contact-free fast path in k_pre appends each env it gives up on to the
-general-path list (one wave-aggregated atomic per wave); k_gen_solve_g and
-k_gen_toi then run over that list.  Round 2 recorded a GPU fault in a
+general-path list (one wave-aggregated atomic per wave); k_gen_solve_g
+then runs over that list.  Round 2 recorded a GPU fault in a
 variant of that list code on the ffa class.  Here
 the list is driven to its maximum -- all N envs, every step -- on the ffa
 class (C5 shard: FFA4, 16 heals, 16 randomized boxes, x16384) and on the 2v2
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 import golden_replay as gr  # noqa: E402
 from masurvival import abi  # noqa: E402
 from gpu_util import class_missing  # noqa: E402
-from masurvival.config import C3_CONFIG, C5_CONFIG, ResolvedConfig, pcg64_state  # noqa: E402
+from masurvival.config import C1_CONFIG, C3_CONFIG, C5_CONFIG, ResolvedConfig, pcg64_state  # noqa: E402
 from masurvival.vec_env import VecMaSurvival  # noqa: E402
 from oracle import OracleEnv  # noqa: E402
 
@@ -70,4 +70,36 @@ def test_all_envs_on_general_path_match_oracle(name, cfg, n, T):
             assert bool(dn[k]) == dd and np.array_equal(r[k], rr), (name, t, e)
             assert np.array_equal(o[k], oo), (name, t, e, gr.diff(o[k], oo))
     assert env.debug_guards()['list_overflow'] == 0
+    env.close()
+
+
+def test_one_lane_bit_is_refused_and_changes_nothing():
+    """Bit 1 of mas_debug_force_general (the one-lane general kernels, removed)
+    is refused with MAS_ERR_UNSUPPORTED and a message naming them; the
+    handle's forced-general mode stays as set, and the next step is bit-exact."""
+    n = 4
+    rc = ResolvedConfig(C1_CONFIG)
+    try:
+        env = VecMaSurvival(C1_CONFIG, n_envs=n, seeds=range(n), auto_reset=True)
+    except abi.MasError as e:
+        class_missing(e)
+    env.force_general(True)
+    lib = abi.load_library()
+    for bits in (2, 3):
+        assert lib.mas_debug_force_general(env._h, bits) == -2  # MAS_ERR_UNSUPPORTED
+        assert b'one-lane' in lib.mas_last_error()
+    ors = [OracleEnv(rc.to_struct(), pcg64_state(e)) for e in range(n)]
+    obs = env.reset().cpu().numpy()
+    for e in range(n):
+        assert np.array_equal(obs[e], ors[e].reset()), e
+    a = np.random.default_rng(11).integers(0, HI, size=(n, rc.n_agents, 6)).astype(np.int8)
+    o, r, dn, _ = env.step(torch.as_tensor(a, device=env.device))
+    assert env.debug_counters()['phys_general_envs'] == n  # still forced onto the general path
+    o, r, dn = o.cpu().numpy(), r.cpu().numpy(), dn.cpu().numpy()
+    for e in range(n):
+        oo, rr, dd = ors[e].step(a[e])
+        if dd:
+            oo = ors[e].reset()
+        assert bool(dn[e]) == dd and np.array_equal(r[e], rr), e
+        assert np.array_equal(o[e], oo), (e, gr.diff(o[e], oo))
     env.close()
