@@ -62,6 +62,11 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
                         const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
                         float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
                         int64_t ld, float* partials, hipStream_t s, bool rm);
+bool policy_train_dw3_ok(int D, int64_t M, int64_t ld);
+hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
+                            const int8_t* act, const float* old_logp, const float* adv, const float* ret, float clip,
+                            float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
+                            float* partials, float* dw3_out, float* scratch, hipStream_t s);
 int policy_rm_feature(int col);
 int64_t policy_adam_scratch();
 hipError_t policy_adam(int64_t n, float* p, const float* g, float* m, float* v, float grad_scale, float max_norm,
@@ -1235,6 +1240,25 @@ int mas_policy_train_ld(const void* packed, int32_t obs_dim, int64_t n_rows, con
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_ld: x must be 16-B aligned with a padded row stride");
     HIP_TRY(policy_train(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
                          ent_coef, scale, h1, h2, da1, da2, dz, ld, partials, (hipStream_t)stream, false));
+    return MAS_OK;
+}
+
+int mas_policy_train_dw3(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
+                         const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
+                         float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
+                         float* partials, float* dw3_out, float* scratch, void* stream)
+{
+    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !da1 ||
+        !da2 || !partials || !dw3_out || !scratch || ld < n_rows)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3: bad argument");
+    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3: x must be 16-B aligned with a padded row stride");
+    if (!policy_train_dw3_ok(obs_dim, n_rows, ld))
+        return fail(MAS_ERR_UNSUPPORTED, "mas_policy_train_dw3: needs the persistent train kernel on every row "
+                                         "(n_rows a multiple of 256, 129 <= obs_dim <= 160, ld even and at most "
+                                         "2^32 / 514, MAS_POL_DB and MAS_POL_DW3 not 0): use mas_policy_train_ld");
+    HIP_TRY(policy_train_dw3(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
+                             ent_coef, scale, h1, da1, da2, ld, partials, dw3_out, scratch, (hipStream_t)stream));
     return MAS_OK;
 }
 

@@ -26,7 +26,9 @@
 //                (clipped surrogate + value MSE - entropy bonus), and the
 //                backward data path dz -> dA2 -> dA1 in the same registers;
 //                writes h1, h2, dA1, dA2, dz feature-major ([F][M] bf16) for
-//                the weight-gradient GEMMs and per-block loss partials.
+//                the weight-gradient GEMMs and per-block loss partials
+//                (k_policy_train_db<.., DW3>: dW3 and db3 summed inside, h2
+//                and dz not written).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdlib>
@@ -603,6 +605,8 @@ struct TrainArgs {
     int64_t ld;             // feature-major: their row stride (>= M; a power of two costs HBM bandwidth);
                             // RM: the row stride of h1 / h2 (>= 257: column 256 holds the ones)
     float* partials;        // [gridDim.x][4]: sum pg, sum (v-ret)^2, sum entropy, clipped count
+    float* dw3;             // k_policy_train_db<.., DW3>: [gridDim.x][16 * 256 + 16] partial dW3, db3 records
+    int64_t bpw;            // k_policy_train_db<.., DW3>: consecutive 256-row blocks per workgroup (0: grid-stride)
 };
 
 // Feature-major activation store of one 32-row M-tile fragment (16 features
@@ -1244,7 +1248,57 @@ __device__ __forceinline__ void land_db()
     lds_barrier();
 }
 
-template <int KS, bool OFF32>
+// DW3: the layer-3 weight gradient accumulated in the kernel (dW3 = dz h2^T,
+// db3 = row sums of dz, over the workgroup's rows) instead of storing h2 and
+// dz for k_dw_lds<16, 4>, and summed exactly as k_dw_lds<16, 4> sums it: per
+// output element one v_mfma_f32_32x32x16_bf16 per 16 consecutive rows (dz
+// the A operand, its rows 16..31 padding; row 16 s + 8 h + j in element j of
+// lane half h), rows ascending from the record's first; db3 the bf16 dz
+// added row by row in fp32.  With the rows split over the workgroups as
+// policy_dw splits them (TrainArgs::bpw consecutive blocks each) the records,
+// and k_dw_reduce's sums of them, are bit-identical to the unfused path's.
+// A weight gradient sums over batch rows, which sit on the lanes here, so dz
+// and h2 cross LDS once: phase E's stage holds only W3^T (16 KiB), and the
+// 56 KiB behind it are idle until phase F's copies.
+//   staging area  dz image [256 rows][16 outputs] bf16 (32-B rows, 8 KiB),
+//                 then one 64-feature chunk of h2 [256 rows][64] bf16 with
+//                 192-B rows (48 KiB): lane (r, h) writes its fragment
+//                 h2[mo][s] as one 16-B word at column 32 m + 16 s + 8 h, so
+//                 column i of 16-column tile t = 2 m + s is feature
+//                 16 t + dw3_feat(i) of the chunk.
+//   per chunk c   every wave writes its 32 rows, barrier, then waves 2 c and
+//                 2 c + 1 (wave w owns the 32 features of M-tile w) walk the
+//                 256 rows in 16 k-steps: both operands by ds_read_b64_tr_b16
+//                 (a lane half reads 4 rows x 64 B of h2: at 48 dwords per row
+//                 banks 0, 48, 32, 16 + 0..15, conflict-free), one MFMA each;
+//                 barrier before the next chunk overwrites.  In chunk 0 wave
+//                 2 (idle there) adds the block's dz rows to the db3 sums.
+// The 16 real output rows are registers 0..7 of the 32x32 tile on both lane
+// halves: 8 accumulator registers live across the blocks (registers 8..15,
+// the padding rows, are zeroed per chunk and dropped); the db3 sums live in
+// LDS.  After the block loop the workgroup writes one k_dw_lds-format record
+// [16][256] + [16] (k_dw_reduce sums them: no atomics, a fixed order).
+// Without the 64 h2 stores phases C and D carry 32 h1 stores each, so every
+// landing stays a counted wait.
+constexpr int kD3DzB = 32;                      // dz image row stride (bytes)
+constexpr int kD3HB = 192;                      // h2 chunk image row stride (bytes): 48 dwords
+constexpr int kD3H0 = kDRows * kD3DzB;          // byte offset of the h2 chunk image in the staging area
+constexpr int kD3Rec = kO * kH + kO;            // floats of one record
+static_assert((kLdsFrag - kBk0 * 64) * 16 >= kD3H0 + kDRows * kD3HB, "the staging area fits behind W3^T");
+__host__ __device__ inline int dw3_feat(int i) { return 8 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3); }
+typedef short s4v __attribute__((ext_vector_type(4)));
+typedef float f8v __attribute__((ext_vector_type(8)));
+// one 32x32x16 operand fragment (8 consecutive batch rows): two transposed reads, STEP4 = 4 rows apart
+template <int STEP4>
+__device__ __forceinline__ bf8 tr_frag(const uint8_t* p)
+{
+    typedef __attribute__((address_space(3))) s4v lds_s4v;
+    const s4v a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)p);
+    const s4v b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(p + STEP4));
+    return __builtin_bit_cast(bf8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+template <int KS, bool OFF32, bool DW3 = false>
 __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, int64_t nblk)
 {
     static_assert(KS > 0, "compile-time layer-1 depth");
@@ -1273,16 +1327,27 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         store_rows2<OFF32>(base, LD, row, t, h, v);
         __builtin_amdgcn_sched_barrier(0);
     };
-    const int64_t b0 = blockIdx.x;
+    // DW3: this wave's dW3 tile, rows crow(i, h) < 16 (registers 0..7) x feature column l & 31 of
+    // M-tile wv; wave 2's db3 sums in LDS
+    f8v acc3 = f8v{};
+    __shared__ float dbl[DW3 ? kO : 1];
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    if (DW3 && wv == 2 && l0 < kO) dbl[l0] = 0.0f;
+    // the workgroup's blocks: b0, b0 + bstep, .. < bend (grid-stride; DW3 with
+    // A.bpw > 0: A.bpw consecutive blocks, k_dw_lds's split of the rows)
+    const bool seq = DW3 && A.bpw > 0;
+    const int64_t b0 = seq ? (int64_t)blockIdx.x * A.bpw : (int64_t)blockIdx.x;
+    const int64_t bstep = seq ? 1 : (int64_t)gridDim.x;
+    const int64_t bend = seq && b0 + A.bpw < nblk ? b0 + A.bpw : nblk;
     // the prologue's copies land before the loop (the same order as landing
     // them in the first block's phase A), so the loop's phase-A wait is always
     // the counted one: no path reaches it with fewer VMEM ops after the
     // copies than it counts (scripts/check_policy_waits.py checks every path)
-    if (b0 < nblk) {
+    if (b0 < bend) {
         copy_db(buf(0), F + Lo.w1(), (KS < kKc ? KS : kKc) * kMT * 64);
         land_db<0>();
     }
-    for (int64_t blk = b0; blk < nblk; blk += gridDim.x) {
+    for (int64_t blk = b0; blk < bend; blk += bstep) {
         // the lane index made opaque per block: keeps the compiler from
         // hoisting the blocks' LDS and store addresses out of the loop (held
         // live across it they spilled)
@@ -1336,12 +1401,12 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
             if (hf == 0) land_db<NCH == 1 ? KS : 0>();
-            else land_db<64>();  // phase C: 64 h1 stores after them
+            else land_db<DW3 ? 32 : 64>();  // phase C: 64 h1 stores after them (DW3: 32)
             const bf8* wl2 = buf(sc);
             if (hf == 0) {
                 copy_db(buf(sc + 1), F + Lo.w23() + kHalf * 64, kHalf * 64);
 #pragma unroll
-                for (int mt = 0; mt < kMT; ++mt) st2(A.h1, row, mt, h, h1[mt]);  // 64 stores
+                for (int mt = 0; mt < (DW3 ? kMT / 2 : kMT); ++mt) st2(A.h1, row, mt, h, h1[mt]);  // 64 stores (DW3: 32)
             } else {
                 copy_db(buf(sc + 1), F + Lo.wbk(), kBk0 * 64);
                 // the loss inputs of the row (read in phase E)
@@ -1351,8 +1416,12 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
                 adv = A.adv[row];
                 old_lp = A.old_logp[row];
                 ret = A.ret[row];
+                // 32 stores: the first h2 half; DW3 (h2 is not stored): the second h1 half
 #pragma unroll
-                for (int mt = 0; mt < kMT / 2; ++mt) st2(A.h2, row, mt, h, h2[mt]);  // 32 stores
+                for (int mt = 0; mt < kMT / 2; ++mt) {
+                    if (DW3) st2(A.h1, row, kMT / 2 + mt, h, h1[kMT / 2 + mt]);
+                    else st2(A.h2, row, mt, h, h2[mt]);
+                }
             }
 #pragma unroll
             for (int q = 0; q < kMT / 2; ++q) {
@@ -1384,11 +1453,14 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         // counted: the compiler may combine the six 2-B / 4-B loads into fewer
         // instructions, and a count above the real one would stop waiting too
         // early; counting fewer only over-waits)
+        // (DW3: the second h1 half's 32 stores)
         land_db<32>();
         const bf8* wb = buf(sc);
         copy_db(buf(sc + 1), F + Lo.wbk() + kBk0 * 64, kBk1 * 64);
+        if (!DW3) {
 #pragma unroll
-        for (int mt = kMT / 2; mt < kMT; ++mt) st2(A.h2, row, mt, h, h2[mt]);  // 32 stores
+            for (int mt = kMT / 2; mt < kMT; ++mt) st2(A.h2, row, mt, h, h2[mt]);  // 32 stores
+        }
         float dz[kO];
 #pragma unroll
         for (int o = 0; o < kO; ++o) dz[o] = 0.0f;
@@ -1449,15 +1521,16 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
             st[1] += dv * dv;
             st[2] += ent;
             st[3] += fabsf(ratio - 1.0f) > A.clip ? 1.0f : 0.0f;
+            if (!DW3) {
 #pragma unroll
-            for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
+                for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
+            }
         }
         bf8 dzf[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) dzf[i >> 3][i & 7] = (__bf16)dz[i];
         bf8 da2[kMT][2];
-#pragma unroll
-        for (int mo = 0; mo < kMT; ++mo) {
+        auto da2_tile = [&](int mo) {
             f16v g = f16v{};
             g = mfma(wb[(mo * 2) * 64 + l], dzf[0], g);
             g = mfma(wb[(mo * 2 + 1) * 64 + l], dzf[1], g);
@@ -1467,16 +1540,81 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
                 da2[mo][i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
             }
             st2(A.da2, row, mo, h, da2[mo]);  // 64 stores
+        };
+        if (!DW3) {
+#pragma unroll
+            for (int mo = 0; mo < kMT; ++mo) da2_tile(mo);
+        } else {
+            // the staging area behind W3^T: the dz image, then the h2 chunk
+            uint8_t* sg = reinterpret_cast<uint8_t*>(const_cast<bf8*>(wb) + kBk0 * 64);
+            const int rl = wv * 32 + (l & 31);  // the lane's row of the block
+            if (h == 0) {  // the row's 16 bf16 dz (lane half 1 holds zeros: not a row)
+                *reinterpret_cast<bf8*>(sg + rl * kD3DzB) = dzf[0];
+                *reinterpret_cast<bf8*>(sg + rl * kD3DzB + 16) = dzf[1];
+            }
+            uint8_t* hw = sg + kD3H0 + rl * kD3HB + 16 * h;
+            // transposed reads of the 32x32x16 operands (lane (r, h): row r, k = 8 h + j): lane
+            // 4 q + p of 16-lane group g supplies batch row 8 h + q (then + 4), columns 4 p .. 4 p + 3
+            // of outputs 0..15 (A; lanes r >= 16 read them again: padded rows, discarded) or of the
+            // tile's 16-column half g & 1 (B)
+            const int r0 = 8 * h + ((l >> 2) & 3);
+            const uint8_t* ar = sg + r0 * kD3DzB + 8 * (l & 3);
+            const uint8_t* br = sg + kD3H0 + r0 * kD3HB + 64 * (wvu & 1) + 32 * ((l >> 4) & 1) + 8 * (l & 3);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    *reinterpret_cast<bf8*>(hw + 64 * m) = h2[2 * c + m][0];
+                    *reinterpret_cast<bf8*>(hw + 64 * m + 32) = h2[2 * c + m][1];
+                }
+                da2_tile(2 * c);
+                lds_barrier();  // the chunk's image (and dz) is complete
+                if ((wvu >> 1) == c) {  // wave-uniform: EXEC stays all ones for the transposed reads
+                    // k_dw_lds<16, 4>'s sum: one 32x32x16 MFMA per 16 rows, rows ascending
+                    f16v acc = f16v{};
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) acc[i] = acc3[i];
+#pragma unroll
+                    for (int ks = 0; ks < kDRows / 16; ++ks) {
+                        const bf8 a = tr_frag<4 * kD3DzB>(ar + ks * 16 * kD3DzB);
+                        const bf8 b = tr_frag<4 * kD3HB>(br + ks * 16 * kD3HB);
+                        acc = mfma(a, b, acc);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) acc3[i] = acc[i];
+                }
+                if (c == 0 && wvu == 2) {
+                    // db3 as k_dw_lds sums it: output l & 15's bf16 dz added row by row
+                    // (every 16-lane group runs the same sum; the sums live in LDS)
+                    float bs = dbl[l & 15];
+                    const uint8_t* dr = sg + ((l >> 2) & 3) * kD3DzB + 8 * (l & 3);
+#pragma unroll 8
+                    for (int k4 = 0; k4 < kDRows / 4; ++k4) {
+                        typedef __attribute__((address_space(3))) s4v lds_s4v;
+                        const s4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(dr + k4 * 4 * kD3DzB));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            bs += __builtin_bit_cast(float, (uint32_t)(uint16_t)v[e] << 16);
+                    }
+                    if (l < kO) dbl[l] = bs;
+                }
+                da2_tile(2 * c + 1);
+                // every wave has read the chunk before the next one overwrites
+                // it (the last chunk: phase F's landing barrier, before its copies)
+                if (c < 3) lds_barrier();
+            }
         }
         ++sc;
         // ---- F, G: W2^T halves; dA1
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            if (hf == 0) land_db<96>();  // phase E: 32 h2 + 64 dA2 stores (+ 16 dz) after them
+            // phase E: 32 h2 + 64 dA2 stores (+ 16 dz) after them (DW3: the 64 dA2 stores;
+            // its DS traffic on the staging area is retired by the landing's lgkmcnt(0))
+            if (hf == 0) land_db<DW3 ? 64 : 96>();
             else land_db<32>();          // phase F: 32 dA1 stores
             const bf8* W2T = buf(sc);
             if (hf == 0) copy_db(buf(sc + 1), F + Lo.wbk() + (kBk0 + kBk1) * 64, kBk1 * 64);
-            else if (blk + gridDim.x < nblk) copy_db(buf(sc + 1), F + Lo.w1(), (KS < kKc ? KS : kKc) * kMT * 64);
+            else if (blk + bstep < bend) copy_db(buf(sc + 1), F + Lo.w1(), (KS < kKc ? KS : kKc) * kMT * 64);
 #pragma unroll
             for (int q = 0; q < kMT / 2; ++q) {
                 const int mt = kMT / 2 * hf + q;
@@ -1495,6 +1633,21 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         }
     }
     const int l = l0;
+    int64_t be = b0;  // the workgroup's first block, for the epilogue
+    if (DW3) {
+        // (re-read from the workgroup id behind an opaque copy: b0 itself,
+        // held in a vector register pair across the block loop, spilled)
+        uint32_t bx = blockIdx.x;
+        asm volatile("" : "+s"(bx));
+        be = seq ? (int64_t)bx * A.bpw : (int64_t)bx;
+        // the workgroup's record [16][256] + [16]: wave w writes M-tile w's
+        // columns of the 16 output rows crow(i, h), wave 2 the db3 sums
+        float* rec = A.dw3 + (int64_t)bx * kD3Rec;
+        const int f0 = 32 * wv + 16 * ((l >> 4) & 1) + dw3_feat(l & 15);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rec[crow(i, l >> 5) * kH + f0] = acc3[i];
+        if (wv == 2 && l < kO) rec[kO * kH + l] = dbl[l];
+    }
     // per-workgroup loss partials: row 2 b0 (this workgroup's first block), zeros in the
     // other rows of its blocks (two 128-row partial rows per 256-row block)
 #pragma unroll
@@ -1505,11 +1658,11 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         if (l == 0) red[wv * 4 + k] = v;
     }
     __syncthreads();
-    for (int64_t blk = b0; blk < nblk; blk += gridDim.x) {
+    for (int64_t blk = be; blk < bend; blk += bstep) {
         if (threadIdx.x < 8) {
             const int k = (int)threadIdx.x & 3;
             float v = 0.0f;
-            if (blk == b0 && threadIdx.x < 4) {
+            if (blk == be && threadIdx.x < 4) {
 #pragma unroll
                 for (int w = 0; w < kDW; ++w) v += red[w * 4 + k];
             }
@@ -1915,10 +2068,10 @@ hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, vo
     return hipGetLastError();
 }
 
-hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
-                        const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
-                        float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
-                        int64_t ld, float* partials, hipStream_t s, bool rm)
+static pol::TrainArgs train_args(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
+                                 const int8_t* act, const float* old_logp, const float* adv, const float* ret,
+                                 float clip, float vf_coef, float ent_coef, float scale, void* h1, void* h2,
+                                 void* da1, void* da2, void* dz, int64_t ld, float* partials, float* dw3)
 {
     pol::TrainArgs A;
     A.ld = ld;
@@ -1941,23 +2094,103 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
     A.da2 = (__bf16*)da2;
     A.dz = (__bf16*)dz;
     A.partials = partials;
+    A.dw3 = dw3;
+    A.bpw = 0;
+    return A;
+}
+
+// CUs of the current device: the persistent train kernel's workgroups
+static int train_ncu()
+{
+    static int ncu = 0;
+    if (ncu == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+            ncu = 256;
+    }
+    return ncu;
+}
+// the persistent double-buffered kernel takes the minibatch's full 256-row
+// blocks: feature-major pair stores with 32-bit offsets (o32), a compile-time
+// layer-1 depth; MAS_POL_DB=0 (read per call): never
+static bool train_db_ok(bool o32, int ks1, int64_t M, int64_t ld)
+{
+    const char* db = getenv("MAS_POL_DB");
+    return o32 && (ks1 == 10 || ks1 == 9) && ((M | ld) & 1) == 0 && M / pol::kDRows > 0 && !(db && db[0] == '0');
+}
+static bool train_o32(int64_t ld)
+{
     // MAS_POL_FORCE_OFF64=1 (test hook, read per call): the 64-bit store
     // offsets that only buffers over 4 GB take, on any size
     const char* f64 = getenv("MAS_POL_FORCE_OFF64");
-    const bool o32 = ld <= pol::kOff32Ld && !(f64 && f64[0] == '1');
+    return ld <= pol::kOff32Ld && !(f64 && f64[0] == '1');
+}
+static int dw_blocks(int64_t K);
+// Workgroups (= partial records) of the train kernel's DW3 form and the
+// consecutive blocks each takes.  Where policy_dw's split of the M rows
+// falls on 256-row blocks and fills the GPU as well (the trainer's
+// minibatches), that split: every record, and so dW3 and db3, is then
+// bit-identical to the unfused path's.  Otherwise one workgroup per CU (up
+// to 256) striding over the blocks (*bpw = 0): the same sums in another order.
+static int dw3_grid(int64_t M, int64_t* bpw)
+{
+    const int64_t nfull = M / pol::kDRows, cap = train_ncu() < 256 ? train_ncu() : 256;
+    const int64_t wide = nfull < cap ? nfull : cap;
+    const int nb = dw_blocks(M);
+    int64_t kc = (M + nb - 1) / nb;
+    kc = (kc + pol::kDwKT - 1) / pol::kDwKT * pol::kDwKT;
+    const int64_t nbu = (M + kc - 1) / kc;
+    if (kc % pol::kDRows == 0 && nbu >= wide) {
+        *bpw = kc / pol::kDRows;
+        return (int)nbu;
+    }
+    *bpw = 0;
+    return (int)wide;
+}
+
+// The train kernel with the layer-3 weight gradient accumulated inside
+// (k_policy_train_db<.., DW3>): h2 and dz are neither stored nor read, the
+// workgroups' records go to `scratch` (policy_dw_scratch(16, 256, M) floats)
+// and k_dw_reduce writes dw3_out [16 * 256 + 16].  Only where the persistent
+// kernel covers every row: its conditions and M % 256 == 0 (a partial last
+// block runs k_policy_train, which cannot accumulate); MAS_POL_DW3=0 (read
+// per call): never.  policy_train_dw3_ok false: nothing is launched or written.
+bool policy_train_dw3_ok(int D, int64_t M, int64_t ld)
+{
+    const char* e = getenv("MAS_POL_DW3");
+    return train_db_ok(train_o32(ld), (D + 15) / 16, M, ld) && M % pol::kDRows == 0 && !(e && e[0] == '0');
+}
+
+hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
+                            const int8_t* act, const float* old_logp, const float* adv, const float* ret, float clip,
+                            float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
+                            float* partials, float* dw3_out, float* scratch, hipStream_t s)
+{
+    pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
+                                  scale, h1, nullptr, da1, da2, nullptr, ld, partials, scratch);
+    const int grid = dw3_grid(M, &A.bpw);
+    auto kd = A.ks1 == 10 ? pol::k_policy_train_db<10, true, true> : pol::k_policy_train_db<9, true, true>;
+    hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, M / pol::kDRows);
+    const int64_t n = pol::kD3Rec;
+    hipLaunchKernelGGL(pol::k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, grid, scratch, dw3_out);
+    return hipGetLastError();
+}
+
+hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
+                        const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
+                        float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
+                        int64_t ld, float* partials, hipStream_t s, bool rm)
+{
+    const pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
+                                        scale, h1, h2, da1, da2, dz, ld, partials, nullptr);
+    const bool o32 = train_o32(ld);
     // the persistent double-buffered kernel for the full 256-row blocks of the
     // PPO update's store mode (feature-major, two rows per lane, 32-bit
     // offsets, compile-time layer-1 depth), k_policy_train for the rest;
     // MAS_POL_DB=0: k_policy_train_cw / k_policy_train only
-    const char* db = getenv("MAS_POL_DB");
     const int64_t nfull = M / pol::kDRows;
-    if (!rm && o32 && (A.ks1 == 10 || A.ks1 == 9) && ((M | ld) & 1) == 0 && nfull > 0 && !(db && db[0] == '0')) {
-        static int ncu = 0;
-        if (ncu == 0) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-                ncu = 256;
-        }
+    if (!rm && train_db_ok(o32, A.ks1, M, ld)) {
+        const int ncu = train_ncu();
         const int64_t grid = nfull < ncu ? nfull : ncu;
         auto kd = A.ks1 == 10 ? pol::k_policy_train_db<10, true> : pol::k_policy_train_db<9, true>;
         hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, nfull);
@@ -2013,7 +2246,16 @@ static int dw_blocks(int64_t K)
     const int64_t b = K / 2048;
     return (int)(b < 1 ? 1 : (b > 256 ? 256 : b));
 }
-int64_t policy_dw_scratch(int F, int G, int64_t K) { return (int64_t)dw_blocks(K) * ((int64_t)F * G + F); }
+// (F = 16 also holds the records of policy_train_dw3: one per workgroup, up to 256)
+int64_t policy_dw_scratch(int F, int G, int64_t K)
+{
+    int64_t nb = dw_blocks(K);
+    if (F == pol::kO) {
+        const int64_t nfull = K / pol::kDRows, g = nfull < 256 ? nfull : 256;
+        nb = nb < g ? g : nb;
+    }
+    return nb * ((int64_t)F * G + F);
+}
 
 hipError_t policy_dw(int F, int G, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, float* out,
                      float* scratch, hipStream_t s)

@@ -90,6 +90,9 @@ SIGNATURES = {
     'mas_policy_train_ld': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                       c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
                             + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
+    'mas_policy_train_dw3': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+                             + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
     'mas_policy_train_rm': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                       c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
                             + [c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
@@ -103,6 +106,11 @@ SIGNATURES = {
     'mas_last_error': (c_char_p, []),
     'mas_abi_version': (c_int32, []),
 }
+# additions within ABI version 3 that an older build of the library (an A/B
+# variant loaded through MAS_LIB) may lack; their callers test with hasattr
+OPTIONAL = {'mas_policy_train_dw3'}
+
+MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # MAS_LIB: an alternative build of the library (A/B variants, libmas_<name>.so)
@@ -124,6 +132,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         raise MasError(f'HIP extension not built: {path} missing (run __graft_entry__.build())')
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

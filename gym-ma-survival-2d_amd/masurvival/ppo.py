@@ -30,7 +30,7 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .abi import check, load_library
+from .abi import MAS_ERR_UNSUPPORTED, check, load_library
 
 HEADS = (3, 3, 3, 2, 2, 2)
 N_LOGITS = sum(HEADS)
@@ -407,26 +407,40 @@ class FusedPolicy:
             # Row stride ld = M + _ACT_PAD: a power-of-two stride (the 4.2M-row minibatch) puts every
             # feature row on the same HBM channels (mas_policy_train_ld)
             ld = M + _ACT_PAD
-            h1, h2 = torch.empty((257, ld), **bf), torch.empty((257, ld), **bf)
+            h1 = torch.empty((257, ld), **bf)
             h1[256] = 1.0
-            h2[256] = 1.0
-            self._bufs = {'M': M, 'ld': ld, 'h1': h1, 'h2': h2,
+            # h2 / dz: _buffers_l3, only when a call stores them (mas_policy_train_dw3 does not)
+            self._bufs = {'M': M, 'ld': ld, 'h1': h1,
                           'da1': torch.empty((256, ld), **bf), 'da2': torch.empty((256, ld), **bf),
-                          'dz': torch.empty((16, ld), **bf),
                           'part': torch.empty((nb, 4), dtype=torch.float32, device=self.device)}
         return self._bufs
+
+    def _buffers_l3(self, M):
+        """_buffers(M) with the layer-3 activations h2 [257, ld] (row 256: ones)
+        and dz [16, ld], which only the unfused path stores."""
+        B = self._buffers(M)
+        if 'h2' not in B:
+            bf = dict(dtype=torch.bfloat16, device=self.device)
+            B['h2'] = torch.empty((257, B['ld']), **bf)
+            B['h2'][256] = 1.0
+            B['dz'] = torch.empty((16, B['ld']), **bf)
+        return B
+
+    def _dw_buffers(self, F, M):
+        """(split-K scratch, out [F * 256 + F]) of a layer's weight-gradient kernel."""
+        key = ('dw', F, M)
+        if key not in self._dwbuf:
+            n = int(self.lib.mas_policy_dw_scratch(F, 256, M))
+            self._dwbuf[key] = (torch.empty((n,), dtype=torch.float32, device=self.device),
+                                torch.empty((F * 256 + F,), dtype=torch.float32, device=self.device))
+        return self._dwbuf[key]
 
     def _dw(self, a, h, F, M, into=None):
         """(a[:, :M] @ h[:256, :M]^T, a.sum(1)) in fp32 via mas_policy_dw.
         into: (weight, bias) fp32 tensors that are one contiguous span of
         F * 256 + F floats (the flat gradient buffer of FusedAdam): the sums
         land there directly and (None, None) is returned."""
-        key = ('dw', F, M)
-        if key not in self._dwbuf:
-            n = int(self.lib.mas_policy_dw_scratch(F, 256, M))
-            self._dwbuf[key] = (torch.empty((n,), dtype=torch.float32, device=self.device),
-                                torch.empty((F * 256 + F,), dtype=torch.float32, device=self.device))
-        scratch, out = self._dwbuf[key]
+        scratch, out = self._dw_buffers(F, M)
         optr = into[0].data_ptr() if into is not None else out.data_ptr()
         check(self.lib.mas_policy_dw(F, 256, M, ctypes.c_void_p(a.data_ptr()), a.stride(0), ctypes.c_void_p(h.data_ptr()),
                                      h.stride(0), ctypes.c_void_p(optr), ctypes.c_void_p(scratch.data_ptr()),
@@ -461,20 +475,39 @@ class FusedPolicy:
             assert t.is_contiguous()
         if self.layout == 'rm':
             return self._grads_rm(xb, actions, old_logp, adv, ret, cfg)
-        B = self._buffers(M)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        check(self.lib.mas_policy_train_ld(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                           ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef, cfg.ent_coef,
-                                           1.0 / M, ptr(B['h1']), ptr(B['h2']), ptr(B['da1']), ptr(B['da2']),
-                                           ptr(B['dz']), B['ld'], ptr(B['part']), self._stream()))
-        B = {k: (v[:, :M] if k in ('h1', 'h2', 'da1', 'da2', 'dz') else v) for k, v in B.items()}
         p = self.policy
         l1, l2, l3 = p.body[0], p.body[2], p.head
+        # layer 3 inside the train kernel (mas_policy_train_dw3: h2 and dz are
+        # not stored) where the library takes the minibatch that way
+        fused3 = False
+        if '3' in _DW_LAYERS and hasattr(self.lib, 'mas_policy_train_dw3'):
+            B = self._buffers(M)
+            span3 = self._grad_span(l3.weight, l3.bias)
+            scratch3, out3 = self._dw_buffers(16, M)
+            rc = self.lib.mas_policy_train_dw3(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
+                                               ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
+                                               cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['da1']), ptr(B['da2']),
+                                               B['ld'], ptr(B['part']),
+                                               ptr(span3[0] if span3 is not None else out3), ptr(scratch3),
+                                               self._stream())
+            if rc != MAS_ERR_UNSUPPORTED:  # refused (nothing written): the unfused path below
+                check(rc)
+                fused3 = True
+        if not fused3:
+            B = self._buffers_l3(M)
+            check(self.lib.mas_policy_train_ld(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
+                                               ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
+                                               cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['h2']), ptr(B['da1']),
+                                               ptr(B['da2']), ptr(B['dz']), B['ld'], ptr(B['part']), self._stream()))
+        B = {k: (v[:, :M] if k in ('h1', 'h2', 'da1', 'da2', 'dz') else v) for k, v in B.items()}
         # layers 2 / 3: the split-K MFMA kernel (mas_policy_dw) where enabled,
         # else the split-K GEMM over the ones-row trick; layer 1 reads x
         # row-major: a GEMM.  With FusedAdam's flat gradient buffer the dW
         # kernels' sums land in .grad directly (no copy launches)
-        if '3' in _DW_LAYERS and M % 32 == 0:
+        if fused3:
+            g3w, g3b = (None, None) if span3 is not None else (out3[:16 * 256].view(16, 256), out3[16 * 256:])
+        elif '3' in _DW_LAYERS and M % 32 == 0:
             g3w, g3b = self._dw(B['dz'], B['h2'], 16, M, into=self._grad_span(l3.weight, l3.bias))
         else:
             g3 = _splitk_nt(B['dz'], B['h2'])          # [16, 257]

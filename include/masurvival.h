@@ -281,6 +281,24 @@ int mas_policy_train_ld(const void* packed, int32_t obs_dim, int64_t n_rows, con
                         const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
                         float vf_coef, float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
                         int64_t ld, float* partials, void* stream);
+/* mas_policy_train_dw3: mas_policy_train_ld with the layer-3 weight gradient
+ * accumulated inside the train kernel: h2 and dz are neither written nor
+ * read (no buffers for them), and dw3_out [16*256 + 16] receives what
+ * mas_policy_dw(16, 256, ...) computes from them (dW3 row-major, then db3):
+ * bit-identical to it where its split-K records fall on 256-row blocks and
+ * fill the GPU (the trainer's minibatches of 1310720 and 4194304 rows),
+ * else the same fp32 sums of the same bf16 operands in another order;
+ * deterministic from call to call either way.
+ * scratch: mas_policy_dw_scratch(16, 256, n_rows) floats.
+ * Only where the persistent train kernel covers every row: n_rows a multiple
+ * of 256, 16*ceil(obs_dim/16) in {144, 160}, ld even and at most 2^32 / 514;
+ * the environment variables MAS_POL_DW3=0 or MAS_POL_DB=0 (read per call)
+ * switch it off.  Otherwise MAS_ERR_UNSUPPORTED: nothing is launched or
+ * written, and the caller uses mas_policy_train_ld + mas_policy_dw. */
+int mas_policy_train_dw3(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
+                         const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
+                         float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
+                         float* partials, float* dw3_out, float* scratch, void* stream);
 /* mas_policy_train_rm: the same kernel writing the activations ROW-major,
  * each lane storing its own row as 16-B chunks (no lane exchange):
  * h1, h2 [n_rows][ld_h] (ld_h >= 257, a multiple of 8; the caller keeps
