@@ -58,6 +58,9 @@ hipError_t policy_pack(int D, const float* W1, const float* b1, const float* W2,
 hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, void* xb, int64_t xb_stride,
                       uint64_t seed, uint64_t step, int64_t first_row, int8_t* act, float* logp, float* value,
                       hipStream_t s);
+hipError_t policy_act_sel(const void* packed, int D, int64_t n_envs, int n_agents, uint32_t mask, const void* xb,
+                          int64_t xb_stride, uint64_t seed, uint64_t step, int64_t first_row, bool greedy,
+                          int8_t* act, float* logp, float* value, float* logits_out, hipStream_t s);
 hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
                         const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
                         float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
@@ -1202,6 +1205,30 @@ int mas_policy_act_x(const void* packed, int32_t obs_dim, int64_t n_rows, int64_
                                          "of 8 >= 16*ceil(obs_dim/16)), actions 2-B aligned");
     HIP_TRY(policy_act(packed, obs_dim, n_rows, nullptr, const_cast<void*>(x_bf16), x_stride, seed, step, first_row,
                        actions, logp, value, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int mas_policy_act_sel(const void* packed, int32_t obs_dim, int64_t n_envs, int32_t n_agents, uint32_t agent_mask,
+                       int64_t first_row, const void* x_bf16, int64_t x_stride, uint64_t seed, uint64_t step,
+                       int32_t greedy, int8_t* actions, float* logp, float* value, float* logits_out, void* stream)
+{
+    // every check before any HIP call
+    if (n_agents < 1 || n_agents > 32)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: n_agents must be in 1..32");
+    if (agent_mask == 0) return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: agent_mask selects no agent");
+    if (n_agents < 32 && (agent_mask >> n_agents) != 0)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: agent_mask has a bit at or above n_agents");
+    if (n_envs < 0 || n_envs > (INT64_MAX >> 6) || obs_dim <= 0 || first_row < 0)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: bad argument (n_envs, obs_dim or first_row)");
+    if (!packed || !x_bf16 || !actions || !logp || !value)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: null packed, x_bf16, actions, logp or value");
+    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15) ||
+        (reinterpret_cast<uintptr_t>(actions) & 1) || (reinterpret_cast<uintptr_t>(logits_out) & 15))
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: x 16-B aligned with a padded row stride (a multiple "
+                                         "of 8 >= 16*ceil(obs_dim/16)), actions 2-B and logits_out 16-B aligned");
+    if (n_envs == 0) return MAS_OK;
+    HIP_TRY(policy_act_sel(packed, obs_dim, n_envs, n_agents, agent_mask, x_bf16, x_stride, seed, step, first_row,
+                           greedy != 0, actions, logp, value, logits_out, (hipStream_t)stream));
     return MAS_OK;
 }
 

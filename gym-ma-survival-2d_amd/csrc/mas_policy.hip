@@ -22,6 +22,9 @@
 // k_policy_act   rollout: forward + Gumbel-max sampling of the six heads (the
 //                exact RNG of k_sample) -> actions, log-prob, value; also
 //                writes the bf16 copy of x the update reads.
+// k_policy_act_sel  evaluation: k_policy_act's bf16-row form over the agents a
+//                bit mask selects (two policies in one env), sampled or
+//                greedy (per-head arg-max), optionally storing the logits.
 // k_policy_train update: forward, the PPO loss gradient per row
 //                (clipped surrogate + value MSE - entropy bonus), and the
 //                backward data path dz -> dA2 -> dA1 in the same registers;
@@ -392,10 +395,19 @@ constexpr int kHeadOff[6] = {0, 3, 6, 9, 11, 13};
 // k)) and choice are the same operations on the same values as the one-half
 // loop of k_policy_act, and lane l adds the six heads' terms to the log-prob
 // in head order: the same bits.
+//
+// GREEDY (k_policy_act_sel): each head's choice is the first-index arg-max of
+// its logits (a strict > scan from index 0) instead of the Gumbel-max draw; no
+// RNG.  The max, log-sum-exp and the log-prob's sum are the sampler's own, so a
+// sampled row that drew the arg-max of every head has the same log-prob bits.
+// logits_out (k_policy_act_sel only, may be null: wave-uniform): the storing
+// lane also writes its row's z[0..16) -- the 15 logits and the value after the
+// bias, the values the choice above reads -- to logits_out[row][16].
+template <bool GREEDY = false, bool LOGITS = false>
 __device__ __forceinline__ void act_sample_split(const f16v& z3, const float* __restrict__ b3, int l, bool ok,
                                                  int64_t row, uint64_t seed, uint64_t step, int64_t first_row,
                                                  int8_t* __restrict__ act, float* __restrict__ logp,
-                                                 float* __restrict__ value)
+                                                 float* __restrict__ value, float* __restrict__ logits_out = nullptr)
 {
     const bool hi = l >= 32;
     float z[kO];
@@ -432,9 +444,14 @@ __device__ __forceinline__ void act_sample_split(const f16v& z3, const float* __
 #pragma unroll
         for (int k = 0; k < nn; ++k) {
             if (!(k < kHeadN[kA[sl]] || k < kHeadN[kB[sl]])) continue;
-            const uint64_t r = mix64(base + (uint64_t)(hd * 4 + k));
-            const float u = ((float)(r >> 40) + 0.5f) * (1.0f / 16777216.0f);
-            const float g = zz[k] - log_fast(-log_fast(u));
+            float g;
+            if constexpr (GREEDY) {
+                g = zz[k];
+            } else {
+                const uint64_t r = mix64(base + (uint64_t)(hd * 4 + k));
+                const float u = ((float)(r >> 40) + 0.5f) * (1.0f / 16777216.0f);
+                g = zz[k] - log_fast(-log_fast(u));
+            }
             if (k < n && g > bv) {
                 bv = g;
                 best = k;
@@ -465,6 +482,13 @@ __device__ __forceinline__ void act_sample_split(const f16v& z3, const float* __
     ap[2] = (uint16_t)pa1;
     logp[row] = lp;
     value[row] = z[kO - 1];
+    if constexpr (LOGITS) {
+        if (logits_out != nullptr) {
+            float4* lo = reinterpret_cast<float4*>(logits_out + row * kO);
+#pragma unroll
+            for (int o = 0; o < kO; o += 4) lo[o >> 2] = make_float4(z[o], z[o + 1], z[o + 2], z[o + 3]);
+        }
+    }
 }
 
 // KS > 0: compile-time k-step count (obs_dim in (16 (KS-1), 16 KS]) with every
@@ -588,6 +612,79 @@ __global__ __launch_bounds__(64 * kWaves, MAS_POL_OCC_ACT * 4 / kWaves) void k_p
     ap[2] = (uint16_t)packed_a[1];
     logp[row] = lp;
     value[row] = z[kO - 1];
+}
+
+// The k-th (from 0) set bit of mask, k < popcount(mask): five branch-free
+// halvings on the popcount of the lower half of what is left.
+__device__ __forceinline__ int nth_set_bit(uint32_t mask, int k)
+{
+    int pos = 0;
+#pragma unroll
+    for (int w = 16; w >= 1; w >>= 1) {
+        const int c = __popc((mask >> pos) & ((1u << w) - 1u));
+        const bool up = k >= c;
+        pos = up ? pos + w : pos;
+        k = up ? k - c : k;
+    }
+    return pos;
+}
+
+// k_policy_act over selected agents (mas_policy_act_sel): the XIN form of
+// k_policy_act for a batch of n_envs envs of n_agents rows each (row = env *
+// n_agents + agent) in which agent_mask selects m = popcount(mask) agents per
+// env.  The waves tile the n_envs * m logical rows j, 32 per wave; logical row
+// j is physical row (j / m) * n_agents + (the (j % m)-th set bit of the mask),
+// where x is loaded and actions, logp and value (and logits_out) are stored:
+// rows of unselected agents are neither read nor written.  The sampling RNG is
+// keyed by first_row + the physical row -- a selected row draws what
+// k_policy_act draws for it.  An out-of-range lane clamps to the last logical
+// row.  GREEDY: act_sample_split's arg-max form.
+template <int KS, bool GREEDY>
+__global__ __launch_bounds__(64 * kWaves, MAS_POL_OCC_ACT * 4 / kWaves) void k_policy_act_sel(
+    const uint8_t* __restrict__ packed, int ks1, int64_t n_envs, int n_agents, uint32_t mask, int m,
+    const __bf16* __restrict__ xb, int64_t xb_stride, uint64_t seed, uint64_t step, int64_t first_row,
+    int8_t* __restrict__ act, float* __restrict__ logp, float* __restrict__ value, float* __restrict__ logits_out)
+{
+    __shared__ bf8 wl[kLdsFrag];
+    Stage1 S{wl};
+    const Layout Lo{ks1};
+    const bf8* F = reinterpret_cast<const bf8*>(packed);
+    const float* FB = reinterpret_cast<const float*>(packed);
+    const float* B1 = FB + Lo.b1();
+    const int l = threadIdx.x & 63, h = l >> 5;
+    const int64_t M = n_envs * m;  // logical rows
+    const int64_t j0 = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * 32;
+    const bool on = j0 < M;  // wave-uniform
+    const int64_t j = j0 + (l & 31);
+    const bool ok = j < M;
+    // env of the wave's first logical row (wave-uniform 64-bit divide), then
+    // the lane's offset from it: below 32 + m, one 32-bit divide per lane
+    const int64_t env0 = (on ? j0 : 0) / m;
+    const uint32_t d = (uint32_t)((ok ? j : M - 1) - env0 * m);
+    const uint32_t de = d / (uint32_t)m;
+    const int64_t row = (env0 + de) * n_agents + nth_set_bit(mask, (int)(d - de * (uint32_t)m));
+    bf8 h1[kMT][2], h2[kMT][2];
+    const __bf16* xr = xb + row * xb_stride + 8 * h;
+    if constexpr (KS > 0) {
+        bf8 x[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const bf8 v = *reinterpret_cast<const bf8*>(xr + 16 * ks);
+            x[ks] = ok ? v : bf8{};
+        }
+        layer1_reg<KS>(S, F + Lo.w1(), B1, l, on, x, h1);
+    } else {
+        layer1(S, F + Lo.w1(), B1, ks1, l, on,
+               [&](int ks) {
+                   const bf8 v = *reinterpret_cast<const bf8*>(xr + 16 * ks);
+                   return ok ? v : bf8{};
+               },
+               h1);
+    }
+    const f16v z3 = layers23<false>(S, F + Lo.w23(), B1 + kMT * 2 * 16, l, on, h1, h2);  // last barrier
+    if (!on) return;
+    act_sample_split<GREEDY, true>(z3, B1 + 2 * kMT * 2 * 16, l, ok, row, seed, step, first_row, act, logp, value,
+                                   logits_out);
 }
 
 struct TrainArgs {
@@ -2065,6 +2162,24 @@ hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, vo
                                        : ks1 == 9 ? pol::k_policy_act<9, false, false> : pol::k_policy_act<0, false, false>));
     hipLaunchKernelGGL(k, dim3((unsigned)act_blocks(M)), dim3(64 * pol::kWaves), 0, s, (const uint8_t*)packed, D,
                        ks1, M, obs, (__bf16*)xb, xb_stride, seed, step, first_row, act, logp, value);
+    return hipGetLastError();
+}
+
+// mas_policy_act_sel: the selected agents' rows of n_envs whole envs (mask
+// checked by the caller: non-zero, no bit at or above n_agents)
+hipError_t policy_act_sel(const void* packed, int D, int64_t n_envs, int n_agents, uint32_t mask, const void* xb,
+                          int64_t xb_stride, uint64_t seed, uint64_t step, int64_t first_row, bool greedy,
+                          int8_t* act, float* logp, float* value, float* logits_out, hipStream_t s)
+{
+    const int ks1 = (D + 15) / 16;
+    const int m = __builtin_popcount(mask);
+    auto k = greedy ? (ks1 == 10 ? pol::k_policy_act_sel<10, true> : ks1 == 9 ? pol::k_policy_act_sel<9, true>
+                                                                               : pol::k_policy_act_sel<0, true>)
+                    : (ks1 == 10 ? pol::k_policy_act_sel<10, false> : ks1 == 9 ? pol::k_policy_act_sel<9, false>
+                                                                                : pol::k_policy_act_sel<0, false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)act_blocks(n_envs * m)), dim3(64 * pol::kWaves), 0, s,
+                       (const uint8_t*)packed, ks1, n_envs, n_agents, mask, m, (const __bf16*)xb, xb_stride, seed,
+                       step, first_row, act, logp, value, logits_out);
     return hipGetLastError();
 }
 

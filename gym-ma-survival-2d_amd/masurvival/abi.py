@@ -84,6 +84,9 @@ SIGNATURES = {
                                       ctypes.c_uint64, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'mas_policy_act_x': (c_int32, [c_void_p, c_int32, c_int64, c_int64, c_void_p, c_int64, ctypes.c_uint64,
                                    ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mas_policy_act_sel': (c_int32, [c_void_p, c_int32, c_int64, c_int32, ctypes.c_uint32, c_int64, c_void_p, c_int64,
+                                     ctypes.c_uint64, ctypes.c_uint64, c_int32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     'mas_policy_train': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
                          + [c_void_p] * 7),
@@ -108,7 +111,7 @@ SIGNATURES = {
 }
 # additions within ABI version 3 that an older build of the library (an A/B
 # variant loaded through MAS_LIB) may lack; their callers test with hasattr
-OPTIONAL = {'mas_policy_train_dw3'}
+OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel'}
 
 MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 

@@ -7,13 +7,20 @@ Added for the batched build: `--envs N` runs N envs of `VecMaSurvival` on the
 device (auto-reset, random actions drawn on the device) for --max-steps steps
 and reports agent-env-steps/s.
 
+--checkpoint PATH plays a saved policy (PPOTrainer.save, or a bare
+{'policy': state_dict} file) instead of random actions; --opponent PATH puts a
+second checkpoint on the other team; --greedy takes every head's most likely
+action instead of sampling.  With --envs N they run a masurvival.match.Match
+for --max-steps steps and print its result (wins, draws, returns).
+
 --screenshot / --gif record `render(mode='rgb_array')` frames (device state,
 masurvival.render) as in `demo.py:178-209`, written with PIL instead of
 imageio + gifsicle.  Out of scope (pygame): the interactive policy and
 --render (a window); they exit with an error naming the missing feature.
 
 usage: python -m masurvival.demo [random] [--max-steps N] [-c CONFIG.json]
-                                 [--benchmark] [--envs N]"""
+                                 [--benchmark] [--envs N]
+                                 [--checkpoint PATH [--opponent PATH] [--greedy]]"""
 import argparse
 import json
 import pprint
@@ -48,6 +55,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--envs', dest='n_envs', metavar='N', type=int, default=None,
                     help='Batched mode: N device envs (auto-reset) for --max-steps steps (default 100).')
     ap.add_argument('--seed', dest='seed', type=int, default=None, help='Env seed (the reference ignores it).')
+    ap.add_argument('--checkpoint', dest='checkpoint', metavar='PATH', type=str, default=None,
+                    help='Play the policy of this checkpoint instead of random actions.')
+    ap.add_argument('--opponent', dest='opponent', metavar='PATH', type=str, default=None,
+                    help='With --checkpoint: the checkpoint that plays the other team.')
+    ap.add_argument('--greedy', dest='greedy', action='store_true', default=False,
+                    help='With --checkpoint: the most likely action of every head instead of a sample.')
     return ap
 
 
@@ -67,20 +80,23 @@ def check_supported(args) -> None:
         missing.append('rendering to a window (--render)')
     if missing:
         raise SystemExit('not available in the MI355X build: ' + ', '.join(missing))
+    if args.checkpoint is None and (args.opponent is not None or args.greedy):
+        raise SystemExit('--opponent and --greedy need --checkpoint')
 
 
 def demo_env(env, max_steps: Optional[int] = None, print_benchmark: bool = False, seed: Optional[int] = None,
-             record=None):
-    """One episode with a random policy (`demo.py:84-157`): until done or
-    max_steps; `record(t, frame)` gets an rgb_array frame after the reset
-    and after each step; returns (stats, step times)."""
+             record=None, actions=None):
+    """One episode (`demo.py:84-157`): until done or max_steps; `record(t,
+    frame)` gets an rgb_array frame after the reset and after each step;
+    `actions(env, t)` supplies step t's action tuple (default: the random
+    policy, `env.action_space.sample()`); returns (stats, step times)."""
     times: List[float] = []
     t, obs, done = 0, env.reset(seed=seed), False
     env.action_space.seed(seed)
     if record is not None:
         record(t, env.render(mode='rgb_array'))
     while not done:
-        action = env.action_space.sample()
+        action = env.action_space.sample() if actions is None else actions(env, t)
         t0 = time.perf_counter()
         obs, reward, done, info = env.step(action)  # returns host arrays: synchronous
         times.append(time.perf_counter() - t0)
@@ -131,10 +147,51 @@ def demo_batched(config, n_envs: int, steps: int, seed: int = 0):
     return rate
 
 
+def load_checkpoints(args, device):
+    from masurvival.match import load_policy
+    paths = [args.checkpoint] + ([args.opponent] if args.opponent is not None else [])
+    return [load_policy(p, device) for p in paths]
+
+
+def demo_match(config, n_envs: int, steps: int, args):
+    """--envs N with --checkpoint: a Match of the checkpoint (against
+    --opponent, or on every agent) for `steps` steps; prints and returns its
+    result dict."""
+    from masurvival.match import Match
+    from masurvival.vec_env import VecMaSurvival
+    seed = args.seed or 0
+    env = VecMaSurvival(config, n_envs=n_envs, seeds=range(seed, seed + n_envs), auto_reset=True)
+    res = Match(env, load_checkpoints(args, env.device), greedy=args.greedy, seed=seed).run(steps=steps)
+    env.close()
+    pprint.PrettyPrinter().pprint(res)
+    return res
+
+
+def checkpoint_actions(env, args):
+    """The action source of demo_env for --checkpoint: the checkpoint's (and
+    the opponent's) actions on the observation the facade's one-env batched
+    env holds on the device."""
+    from masurvival.match import Actor
+    vec = env._vec
+    actor = Actor(load_checkpoints(args, vec.device), 1, vec.n_agents, vec.obs_dim, vec.device, greedy=args.greedy,
+                  seed=args.seed or 0)
+    x = actor.x_buffer()
+    out = vec._act.new_zeros(vec._act.shape)
+
+    def actions(env, t):
+        x[:, :vec.obs_dim].copy_(vec.obs.reshape(-1, vec.obs_dim))
+        a = actor.act(x, t, out)[0].cpu().numpy()
+        return tuple(a[i].astype(np.int64) for i in range(vec.n_agents))
+    return actions
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     check_supported(args)
     config = load_config(args.env_config_fpath)
+    if args.n_envs is not None and args.checkpoint is not None:
+        demo_match(config, args.n_envs, args.max_steps or 100, args)
+        return 0
     if args.n_envs is not None:
         demo_batched(config, args.n_envs, args.max_steps or 100, args.seed or 0)
         return 0
@@ -148,7 +205,8 @@ def main(argv=None) -> int:
         if args.gif_fpath is not None and t % args.gif_record_interval == 0:
             rec['gif'].append(frame)
     want = args.screenshot_fpath is not None or args.gif_fpath is not None
-    demo_env(env, args.max_steps, args.print_benchmark, args.seed, record if want else None)
+    source = checkpoint_actions(env, args) if args.checkpoint is not None else None
+    demo_env(env, args.max_steps, args.print_benchmark, args.seed, record if want else None, source)
     save_frames(args, rec)
     return 0
 

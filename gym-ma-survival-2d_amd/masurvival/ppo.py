@@ -30,7 +30,7 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .abi import MAS_ERR_UNSUPPORTED, check, load_library
+from .abi import MAS_ERR_UNSUPPORTED, MasError, check, load_library
 
 HEADS = (3, 3, 3, 2, 2, 2)
 N_LOGITS = sum(HEADS)
@@ -358,6 +358,33 @@ class FusedPolicy:
                                         ctypes.c_void_p(xb.data_ptr()), self.Dx, int(seed), int(step),
                                         ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(logp.data_ptr()),
                                         ctypes.c_void_p(value.data_ptr()), self._stream()))
+
+    @torch.no_grad()
+    def act_sel(self, xb, n_agents, agent_mask, seed, step, actions, logp, value, greedy=False, logits=None,
+                first_row=0):
+        """act_x over the agents bit-selected by agent_mask of the whole envs in
+        xb [n_envs * n_agents, Dx] (include/masurvival.h mas_policy_act_sel):
+        only the selected agents' rows are read and only their rows of actions,
+        logp, value (and logits fp32 [M, 16]: 15 logits, then the value) are
+        written, with the values act_x gives them.  greedy: the first-index
+        arg-max of every head instead of a draw (seed / step unused)."""
+        M = xb.shape[0]
+        assert xb.is_contiguous() and xb.dtype == torch.bfloat16 and xb.shape[1] == self.Dx
+        assert actions.is_contiguous() and logp.is_contiguous() and value.is_contiguous()
+        if not hasattr(self.lib, 'mas_policy_act_sel'):
+            raise MasError('the loaded library has no mas_policy_act_sel')
+        n_agents = int(n_agents)
+        assert n_agents == 0 or M % n_agents == 0
+        lp = None
+        if logits is not None:
+            assert logits.is_contiguous() and logits.dtype == torch.float32 and logits.shape == (M, 16)
+            lp = ctypes.c_void_p(logits.data_ptr())
+        check(self.lib.mas_policy_act_sel(ctypes.c_void_p(self.packed.data_ptr()), self.D,
+                                          M // n_agents if n_agents > 0 else 0, n_agents, int(agent_mask),
+                                          int(first_row), ctypes.c_void_p(xb.data_ptr()), self.Dx, int(seed),
+                                          int(step), int(bool(greedy)), ctypes.c_void_p(actions.data_ptr()),
+                                          ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(value.data_ptr()), lp,
+                                          self._stream()))
 
     def _buffers_rm(self, M):
         if self._bufs is None or self._bufs['M'] != M:

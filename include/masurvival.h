@@ -268,6 +268,30 @@ int mas_policy_act_rows(const void* packed, int32_t obs_dim, int64_t n_rows, int
 int mas_policy_act_x(const void* packed, int32_t obs_dim, int64_t n_rows, int64_t first_row, const void* x_bf16,
                      int64_t x_stride, uint64_t seed, uint64_t step, int8_t* actions, float* logp, float* value,
                      void* stream);
+/* mas_policy_act_sel (an addition within ABI version 3): mas_policy_act_x
+ * over the selected agents of whole envs, sampled or greedy -- what lets two
+ * packed policies act in one env.  The slice is n_envs envs of n_agents rows
+ * each (row = env * n_agents + agent; the pointers address the slice's first
+ * row, first_row is its index in the whole batch, as for
+ * mas_policy_act_rows).  Bit a of agent_mask selects agent a of every env:
+ * the kernel runs over the n_envs * popcount(agent_mask) selected rows and
+ * neither reads nor writes the rows of the other agents, so calls with
+ * disjoint masks fill disjoint rows of the same output buffers.  The sampling
+ * RNG is keyed by first_row + the row's index in the slice: a selected row
+ * gets exactly the actions, log-prob and value mas_policy_act_x gives it.
+ * greedy != 0: each head takes the arg-max of its logits (after the bias,
+ * fp32; the lowest index wins a tie) and seed / step are unused; logp is the
+ * log-prob of that choice, bit-identical to a sampled call's that drew it.
+ * logits_out (may be NULL; fp32 [rows][16], 16-B aligned): the selected rows'
+ * 15 logits and then the value, the values the choice was made from.
+ * MAS_ERR_INVALID_ARG, before any device work: n_agents outside 1..32, a zero
+ * agent_mask, a mask bit at or above n_agents, n_envs < 0, a null packed,
+ * x_bf16, actions, logp or value, or an x_stride / alignment mas_policy_act_x
+ * refuses.  n_envs == 0 is MAS_OK and launches nothing. */
+int mas_policy_act_sel(const void* packed, int32_t obs_dim, int64_t n_envs, int32_t n_agents,
+                       uint32_t agent_mask, int64_t first_row, const void* x_bf16, int64_t x_stride,
+                       uint64_t seed, uint64_t step, int32_t greedy,
+                       int8_t* actions, float* logp, float* value, float* logits_out, void* stream);
 int mas_policy_train(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
                      const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
                      float vf_coef, float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
