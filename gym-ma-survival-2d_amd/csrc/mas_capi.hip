@@ -61,6 +61,10 @@ hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, vo
 hipError_t policy_act_sel(const void* packed, int D, int64_t n_envs, int n_agents, uint32_t mask, const void* xb,
                           int64_t xb_stride, uint64_t seed, uint64_t step, int64_t first_row, bool greedy,
                           int8_t* act, float* logp, float* value, float* logits_out, hipStream_t s);
+// dense gather of the selected agents' rows (mas_select.hip)
+hipError_t rows_select(int64_t n_envs, int n_agents, uint32_t mask, const void* x, int64_t x_stride, void* x_out,
+                       int64_t x_out_stride, int x_cols, const int8_t* act, int8_t* act_out, int n_f32,
+                       const float* const* f_in, float* const* f_out, hipStream_t s);
 hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
                         const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
                         float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
@@ -1229,6 +1233,56 @@ int mas_policy_act_sel(const void* packed, int32_t obs_dim, int64_t n_envs, int3
     if (n_envs == 0) return MAS_OK;
     HIP_TRY(policy_act_sel(packed, obs_dim, n_envs, n_agents, agent_mask, x_bf16, x_stride, seed, step, first_row,
                            greedy != 0, actions, logp, value, logits_out, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int mas_rows_select(int64_t n_envs, int32_t n_agents, uint32_t agent_mask, const void* x_bf16, int64_t x_stride,
+                    void* x_out, int64_t x_out_stride, int32_t x_cols, const int8_t* actions, int8_t* actions_out,
+                    int32_t n_f32, const float* const* f32_in, float* const* f32_out, void* stream)
+{
+    // every check before any HIP call
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (n_agents < 1 || n_agents > 32) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: n_agents must be in 1..32");
+    if (agent_mask == 0) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: agent_mask selects no agent");
+    if (n_agents < 32 && (agent_mask >> n_agents) != 0)
+        return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: agent_mask has a bit at or above n_agents");
+    if (n_envs < 0) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: n_envs must not be negative");
+    if (n_f32 < 0 || n_f32 > 4) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: n_f32 must be in 0..4");
+    if (n_f32 > 0 && (!f32_in || !f32_out))
+        return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: n_f32 > 0 with a null f32_in or f32_out pointer array");
+    if (!x_bf16 != !x_out) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: half-null pair (x_bf16, x_out)");
+    if (!actions != !actions_out)
+        return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: half-null pair (actions, actions_out)");
+    for (int f = 0; f < n_f32; ++f) {
+        if (!f32_in[f] != !f32_out[f])
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: half-null pair (f32_in[" + std::to_string(f) + "], f32_out)");
+        if (f32_in[f] && f32_in[f] == f32_out[f])
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: f32_out[" + std::to_string(f) + "] equals its input");
+        if ((addr(f32_in[f]) | addr(f32_out[f])) & 3)
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: f32 arrays must be 4-B aligned");
+    }
+    if (actions) {
+        if (actions == actions_out) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: actions_out equals its input");
+        if ((addr(actions) | addr(actions_out)) & 1)
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: actions arrays must be 2-B aligned");
+    }
+    int64_t widest = 8;
+    if (x_bf16) {
+        if (x_cols <= 0 || (x_cols % 8) != 0 || x_cols > x_stride || x_cols > x_out_stride)
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: x_cols must be a positive multiple of 8, at most "
+                                             "x_stride and x_out_stride");
+        if ((x_stride % 8) != 0 || (x_out_stride % 8) != 0)
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: x_stride and x_out_stride must be multiples of 8");
+        if ((addr(x_bf16) | addr(x_out)) & 15)
+            return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: x_bf16 and x_out must be 16-B aligned");
+        if (x_bf16 == x_out) return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: x_out equals its input");
+        widest = std::max(x_stride, x_out_stride);
+    }
+    if (n_envs > (INT64_MAX >> 8) / widest)
+        return fail(MAS_ERR_INVALID_ARG, "mas_rows_select: n_envs too large (byte offsets past 2^63)");
+    if (n_envs == 0) return MAS_OK;
+    HIP_TRY(rows_select(n_envs, n_agents, agent_mask, x_bf16, x_stride, x_out, x_out_stride, x_cols, actions,
+                        actions_out, n_f32, f32_in, f32_out, (hipStream_t)stream));
     return MAS_OK;
 }
 

@@ -87,6 +87,8 @@ SIGNATURES = {
     'mas_policy_act_sel': (c_int32, [c_void_p, c_int32, c_int64, c_int32, ctypes.c_uint32, c_int64, c_void_p, c_int64,
                                      ctypes.c_uint64, ctypes.c_uint64, c_int32, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    'mas_rows_select': (c_int32, [c_int64, c_int32, ctypes.c_uint32, c_void_p, c_int64, c_void_p, c_int64, c_int32,
+                                  c_void_p, c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
     'mas_policy_train': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
                          + [c_void_p] * 7),
@@ -111,7 +113,7 @@ SIGNATURES = {
 }
 # additions within ABI version 3 that an older build of the library (an A/B
 # variant loaded through MAS_LIB) may lack; their callers test with hasattr
-OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel'}
+OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel', 'mas_rows_select'}
 
 MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 

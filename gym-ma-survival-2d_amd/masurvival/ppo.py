@@ -17,6 +17,13 @@ Multi-GPU (one process per GPU, envs sharded): the only collectives are one
 fp64 all-reduce of (sum adv, sum adv^2, count) per rollout and one flat
 gradient all-reduce (average) per minibatch -- RCCL over xGMI when the process
 group is 'nccl', gloo in the CPU tests.
+
+Self-play (``PPOTrainer(opponent=..., learner_agents=...)``): a frozen opponent
+drives the agents the trained policy does not own.  Both act in one rollout
+(two ``mas_policy_act_sel`` calls per step into one actions buffer); after it
+the learner's rows are gathered once into dense buffers (``mas_rows_select``,
+``RolloutBuffer.learner``), and GAE, the advantage statistics and the update
+run on those alone.
 """
 from __future__ import annotations
 
@@ -78,6 +85,9 @@ class PPOConfig:
     # (mas_step_x) instead of fp32 obs rows the act kernel re-reads and
     # converts; None = whenever the env supports it (same bits either way)
     x_obs: Optional[bool] = None
+    # self-play (PPOTrainer(opponent=...)): copy the learner's weights into the
+    # opponent after every k-th iteration() (lagged self-play); 0 = never
+    opponent_sync_every: int = 0
 
 
 def _split_k(m: int, cap: int = int(os.environ.get('MAS_SPLITK_CAP', '128'))) -> int:
@@ -214,6 +224,89 @@ def adv_normalize(adv, stats, stream=None):
     st = stream if stream is not None else torch.cuda.current_stream(adv.device).cuda_stream
     check(lib.mas_adv_normalize(adv.numel(), ctypes.c_void_p(adv.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
                                 ctypes.c_void_p(st)))
+
+
+def _agent_mask(agents, n_agents, what='agents'):
+    """Bit mask of a list of agent indices (unique, in range, non-empty)."""
+    agents = [int(a) for a in agents]
+    if not agents:
+        raise ValueError(f'{what}: no agent given')
+    if len(set(agents)) != len(agents):
+        raise ValueError(f'{what}: {agents} repeats an agent')
+    if min(agents) < 0 or max(agents) >= n_agents:
+        raise ValueError(f'{what}: {agents} outside 0..{n_agents - 1}')
+    return sum(1 << a for a in agents)
+
+
+def rows_select(n_agents, agent_mask, x=None, x_out=None, x_cols=None, actions=None, actions_out=None, f32=(),
+                stream=None):
+    """Gather the rows of the agents bit-selected by agent_mask into dense
+    tensors (include/masurvival.h mas_rows_select): every input holds whole
+    envs of n_agents rows (row = env * n_agents + agent), every output
+    n_envs * popcount(agent_mask) rows in (env, ascending agent) order.
+    x / x_out: bf16 [rows, stride] with unit column stride (the row strides
+    may differ; columns [0, x_cols) are copied, x_cols defaults to x's
+    width); actions / actions_out: int8 [rows, 6]; f32: up to four (in, out)
+    pairs of fp32 tensors of rows elements.  Pairs left out are skipped.  One
+    launch on the current stream.  A wrong tensor raises ValueError before
+    anything reaches the device."""
+    n_agents, agent_mask = int(n_agents), int(agent_mask)
+    if not 1 <= n_agents <= 32:
+        raise ValueError(f'rows_select: n_agents {n_agents} outside 1..32')
+    if agent_mask <= 0 or agent_mask >> n_agents:
+        raise ValueError(f'rows_select: agent_mask {agent_mask:#x} is zero or has a bit at or above n_agents')
+    m = bin(agent_mask).count('1')
+    f32 = list(f32)
+    if len(f32) > 4:
+        raise ValueError(f'rows_select: at most four fp32 pairs, got {len(f32)}')
+    if (x is None) != (x_out is None) or (actions is None) != (actions_out is None):
+        raise ValueError('rows_select: an input without its output (or the reverse)')
+    pairs = []  # (name, in, out, dtype, rows of in, rows of out)
+    if x is not None:
+        for name, t in (('x', x), ('x_out', x_out)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 8 != 0:
+                raise ValueError(f'rows_select: {name} must be a [rows, stride] tensor with unit column stride and '
+                                 'a row stride that is a multiple of 8')
+        x_cols = int(x.shape[1] if x_cols is None else x_cols)
+        if x_cols <= 0 or x_cols % 8 != 0 or x_cols > x.shape[1] or x_cols > x_out.shape[1]:
+            raise ValueError(f'rows_select: x_cols {x_cols} must be a positive multiple of 8 within both widths')
+        pairs.append(('x', x, x_out, torch.bfloat16, x.shape[0], x_out.shape[0]))
+    if actions is not None:
+        for name, t in (('actions', actions), ('actions_out', actions_out)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 6 or not t.is_contiguous():
+                raise ValueError(f'rows_select: {name} must be a contiguous [rows, 6] tensor')
+        pairs.append(('actions', actions, actions_out, torch.int8, actions.shape[0], actions_out.shape[0]))
+    for k, pr in enumerate(f32):
+        if len(pr) != 2 or not all(isinstance(t, torch.Tensor) and t.is_contiguous() for t in pr):
+            raise ValueError(f'rows_select: f32[{k}] must be an (in, out) pair of contiguous tensors')
+        pairs.append((f'f32[{k}]', pr[0], pr[1], torch.float32, pr[0].numel(), pr[1].numel()))
+    if not pairs:
+        return
+    rows = pairs[0][4]
+    if rows % n_agents != 0:
+        raise ValueError(f'rows_select: {rows} rows are not whole envs of {n_agents} agents')
+    n_envs = rows // n_agents
+    dev = pairs[0][1].device
+    for name, ti, to, dt, ri, ro in pairs:
+        if ti.dtype != dt or to.dtype != dt:
+            raise ValueError(f'rows_select: {name} must be {dt} (got {ti.dtype} -> {to.dtype})')
+        if not (ti.is_cuda and to.is_cuda) or ti.device != dev or to.device != dev:
+            raise ValueError(f'rows_select: {name} must live on one GPU (got {ti.device} -> {to.device})')
+        if ri != rows or ro != n_envs * m:
+            raise ValueError(f'rows_select: {name} has {ri} -> {ro} rows, expected {rows} -> {n_envs * m}')
+        if ti.data_ptr() == to.data_ptr() and ri > 0:
+            raise ValueError(f'rows_select: {name} is gathered onto itself')
+    lib = load_library()
+    if not hasattr(lib, 'mas_rows_select'):
+        raise MasError('the loaded library has no mas_rows_select')
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+    n = len(f32)
+    fin = (ctypes.c_void_p * max(n, 1))(*[pr[0].data_ptr() for pr in f32])
+    fout = (ctypes.c_void_p * max(n, 1))(*[pr[1].data_ptr() for pr in f32])
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    check(lib.mas_rows_select(n_envs, n_agents, agent_mask, ptr(x), x.stride(0) if x is not None else 0, ptr(x_out),
+                              x_out.stride(0) if x is not None else 0, x_cols if x is not None else 0,
+                              ptr(actions), ptr(actions_out), n, fin, fout, ctypes.c_void_p(st)))
 
 
 def gae_reference(rewards, values, dones, gamma, lam, n_agents):
@@ -644,10 +737,10 @@ class FusedAdam:
 
 
 class RolloutBuffer:
-    def __init__(self, T, N, A, D, device):
+    def __init__(self, T, N, A, D, device, with_obs=True):
         self.T, self.N, self.A, self.D = T, N, A, D
         f = dict(device=device, dtype=torch.float32)
-        self.obs = torch.zeros((T + 1, N, A, D), **f)
+        self.obs = torch.zeros((T + 1, N, A, D), **f) if with_obs else None
         self.actions = torch.zeros((T, N, A, 6), device=device, dtype=torch.int8)
         self.logp = torch.zeros((T, N, A), **f)
         self.values = torch.zeros((T + 1, N, A), **f)
@@ -663,6 +756,21 @@ class RolloutBuffer:
         self.adv_sums = self.adv_stats[:2]
         self.gae_scratch = None  # mas_gae's partial sums (made at the first HIP GAE call)
         self.xb = None  # fused path: bf16 policy-input rows [T (+1 with x_obs), N*A, Dx] (mas_policy_act / mas_step_x)
+        # self-play: the learner's rows of this rollout, compacted once per
+        # iteration into a buffer of the same shape with A = its agent count
+        # (alloc_learner); GAE and the update then read only that one
+        self.learner = None
+
+    def alloc_learner(self, m, device, fused=None):
+        """The dense buffer of m learner agents per env: the fields GAE and the
+        update read, `dones` shared with this buffer; on the fused path bf16
+        rows xb [T, N*m, Dx] instead of fp32 obs."""
+        lb = RolloutBuffer(self.T, self.N, m, self.D, device, with_obs=fused is None)
+        lb.dones = self.dones
+        if fused is not None:
+            lb.xb = fused.x_buffer(self.T, self.N * m)
+        self.learner = lb
+        return lb
 
 
 def _allreduce_grads(params, world, group=None):
@@ -691,9 +799,17 @@ class PPOTrainer:
     each epoch: no row gather.  The torch path (random row minibatches,
     autograd) serves the CPU tests and is the numerics reference."""
 
-    def __init__(self, env, cfg: PPOConfig = PPOConfig(), seed: int = 0, group=None):
+    def __init__(self, env, cfg: PPOConfig = PPOConfig(), seed: int = 0, group=None, opponent=None,
+                 learner_agents=None):
+        """opponent: a frozen policy (a PolicyMLP, a checkpoint path or a
+        loaded checkpoint dict, as match.load_policy reads them) that drives
+        the agents outside `learner_agents`; the trained policy acts for and is
+        updated on the rows of `learner_agents` only (default with an
+        opponent: range(n_agents // 2), Match's side 0).  Both None: every
+        agent is the trained policy's and nothing below changes."""
         self.env, self.cfg = env, cfg
         self.device = env.device
+        self.opponent, self.learner_agents = self._resolve_selfplay(env, opponent, learner_agents)
         self.group = group
         self.world = dist.get_world_size(group) if group is not None or dist.is_initialized() else 1
         self.collectives = self.world > 1 if cfg.allreduce is None else bool(cfg.allreduce)
@@ -707,6 +823,8 @@ class PPOTrainer:
         self.gen.manual_seed(seed * 7919 + (dist.get_rank() if dist.is_initialized() else 0))
         self.buf.obs[0].copy_(env.reset())
         self.last_stats = {}
+        self.iterations = 0  # finished iteration() calls (opponent_sync_every)
+        self.opp_fused = None
         self.gae_impl = gae  # the HIP kernel; CPU tests inject gae_reference_into
         self.seed = int(seed) * 1000003 + (dist.get_rank() if dist.is_initialized() else 0)
         self.steps_taken = 0
@@ -738,6 +856,82 @@ class PPOTrainer:
                 self.fused_opt = FusedAdam(self.policy.parameters(), self.opt, self.fused.lib, self.device)
         else:
             self._sync_rollout_policy()
+        if self.learner_agents is not None:
+            self._init_selfplay()
+
+    @staticmethod
+    def _resolve_selfplay(env, opponent, learner_agents):
+        """(frozen opponent PolicyMLP or None, sorted learner agent list or
+        None) from the constructor's arguments, or ValueError."""
+        if opponent is None and learner_agents is None:
+            return None, None
+        A = int(env.n_agents)
+        if not 1 <= A <= 32:
+            raise ValueError(f'self-play: n_agents {A} outside 1..32')
+        if learner_agents is None:
+            learner_agents = range(A // 2)
+        learner_agents = [int(a) for a in learner_agents]
+        _agent_mask(learner_agents, A, 'learner_agents')
+        whole = len(learner_agents) == A
+        if opponent is None:
+            if not whole:
+                raise ValueError(f'learner_agents {learner_agents} leaves agents without a policy: give an opponent')
+            return None, sorted(learner_agents)
+        if whole:
+            raise ValueError('learner_agents must be a proper subset of the agents when an opponent is given')
+        if isinstance(opponent, PolicyMLP):
+            import copy
+            opponent = copy.deepcopy(opponent)
+        else:
+            from .match import load_policy  # (match imports this module)
+            opponent = load_policy(opponent)
+        d = int(opponent.body[0].weight.shape[1])
+        if d != env.obs_dim:
+            raise ValueError(f'opponent obs_dim {d} does not match the env obs_dim {env.obs_dim}')
+        opponent = opponent.to(env.device).float().eval()
+        for p in opponent.parameters():
+            p.requires_grad_(False)
+        return opponent, sorted(learner_agents)
+
+    def _init_selfplay(self):
+        b, A = self.buf, self.buf.A
+        self._lmask = _agent_mask(self.learner_agents, A)
+        self._omask = ((1 << A) - 1) ^ self._lmask
+        self._lidx = torch.tensor(self.learner_agents, dtype=torch.long, device=self.device)
+        self._lsel = torch.zeros((A,), dtype=torch.bool, device=self.device)
+        self._lsel[self._lidx] = True
+        if self.device.type == 'cuda':
+            why = None
+            if self.fused is None:
+                why = 'the fused policy kernels (PPOConfig.fused, hidden 256)'
+            elif not self.x_obs:
+                why = 'the bf16-row rollout (PPOConfig.x_obs, an env with step_x)'
+            elif hasattr(self.env, 'shard_slices'):
+                why = 'an unsharded env'
+            if why is not None:
+                raise ValueError(f'self-play on a GPU needs {why}')
+            if not hasattr(self.fused.lib, 'mas_rows_select') or not hasattr(self.fused.lib, 'mas_policy_act_sel'):
+                raise MasError('the loaded library has no mas_rows_select / mas_policy_act_sel')
+            if self.opponent is not None:
+                self.opp_fused = FusedPolicy(self.opponent, self.env.obs_dim, self.device)
+                self.opp_fused.pack()
+                # the opponent's log-probs and values: written, never read
+                self._opp_out = (torch.empty((b.N * A,), dtype=torch.float32, device=self.device),
+                                 torch.empty((b.N * A,), dtype=torch.float32, device=self.device))
+        elif self.fused is not None:
+            raise ValueError('self-play with the fused kernels needs a GPU env')
+        b.alloc_learner(len(self.learner_agents), self.device, self.fused)
+
+    @torch.no_grad()
+    def sync_opponent(self):
+        """Lagged self-play: the opponent becomes a copy of the learner's
+        current fp32 weights (and is packed again for the kernels)."""
+        if self.opponent is None:
+            raise ValueError('sync_opponent: this trainer has no opponent')
+        for d, s_ in zip(self.opponent.parameters(), self.policy.parameters()):
+            d.copy_(s_)
+        if self.opp_fused is not None:
+            self.opp_fused.pack()
 
     @torch.no_grad()
     def _set_x0(self, obs):
@@ -746,9 +940,9 @@ class PPOTrainer:
         b = self.buf
         b.xb[0][:, :b.D].copy_(obs.reshape(-1, b.D).to(torch.bfloat16))
 
-    def _fwd(self, x):
+    def _fwd(self, x, policy=None):
         with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.cfg.autocast_bf16):
-            return self.policy(x)
+            return (self.policy if policy is None else policy)(x)
 
     @torch.no_grad()
     def _sync_rollout_policy(self):
@@ -762,8 +956,55 @@ class PPOTrainer:
                 d.copy_(s_)
 
     @torch.no_grad()
+    def _rollout_step_selfplay(self, t):
+        """One step with the learner on its agents and the opponent (when
+        there is one) on the others: both fill the same actions[t]."""
+        b = self.buf
+        if self.fused is not None:
+            acts = b.actions[t].view(-1, 6)
+            # one RNG key for both calls: it is keyed by the physical row
+            self.fused.act_sel(b.xb[t], b.A, self._lmask, self.seed, self.steps_taken, acts, b.logp[t].view(-1),
+                               b.values[t].view(-1))
+            if self.opp_fused is not None:
+                self.opp_fused.act_sel(b.xb[t], b.A, self._omask, self.seed, self.steps_taken, acts, *self._opp_out)
+            self.steps_taken += 1
+            self.env.step_x(b.actions[t], b.xb[t + 1], b.rewards[t], b.dones[t])
+            return
+        logits, v = self._fwd(b.obs[t])
+        a, lp = sample_actions(logits, self.gen)
+        if self.opponent is not None:
+            ao, _ = sample_actions(self._fwd(b.obs[t], self.opponent)[0], self.gen)
+            a = torch.where(self._lsel.view(1, -1, 1), a, ao)
+        b.actions[t].copy_(a)
+        b.logp[t].copy_(lp)
+        b.values[t].copy_(v)
+        self.steps_taken += 1
+        self.env.step(b.actions[t], out=(b.obs[t + 1], b.rewards[t], b.dones[t]))
+
+    @torch.no_grad()
+    def _select_learner_rows(self):
+        """The learner's rows of the finished rollout into buf.learner."""
+        b, lb = self.buf, self.buf.learner
+        T = b.T
+        if self.fused is not None:
+            Dx = self.fused.Dx
+            rows_select(b.A, self._lmask, x=b.xb[:T].view(-1, Dx), x_out=lb.xb.view(-1, Dx),
+                        actions=b.actions.view(-1, 6), actions_out=lb.actions.view(-1, 6),
+                        f32=[(b.logp, lb.logp), (b.rewards, lb.rewards)])
+            rows_select(b.A, self._lmask, f32=[(b.values, lb.values)])  # T + 1 row blocks
+            return
+        i = self._lidx
+        lb.obs[:T].copy_(b.obs[:T].index_select(2, i))
+        lb.actions.copy_(b.actions.index_select(2, i))
+        lb.logp.copy_(b.logp.index_select(2, i))
+        lb.rewards.copy_(b.rewards.index_select(2, i))
+        lb.values.copy_(b.values.index_select(2, i))
+
+    @torch.no_grad()
     def rollout_step(self, t):
         b = self.buf
+        if self.learner_agents is not None:
+            return self._rollout_step_selfplay(t)
         if self.fused is not None and hasattr(self.env, 'shard_slices'):
             # sharded env (vec_env.ShardedVecMaSurvival): each shard's policy
             # forward + env step on its own stream, so one shard's act
@@ -817,7 +1058,10 @@ class PPOTrainer:
     @torch.no_grad()
     def finish_rollout(self):
         b, c = self.buf, self.cfg
-        if self.x_obs:
+        if self.learner_agents is not None and self.fused is not None:
+            self.fused.act_sel(b.xb[c.horizon], b.A, self._lmask, self.seed, 0, self._boot[0], self._boot[1],
+                               b.values[c.horizon].view(-1))
+        elif self.x_obs:
             self.fused.act_x(b.xb[c.horizon], self.seed, 0, self._boot[0], self._boot[1], b.values[c.horizon].view(-1))
         elif self.fused is not None:
             self.fused.act(b.obs[c.horizon].view(-1, b.D), self.seed, 0, self._boot[0], self._boot[1],
@@ -825,9 +1069,13 @@ class PPOTrainer:
         else:
             _, v = self._fwd(b.obs[c.horizon])
             b.values[c.horizon].copy_(v)
+        if b.learner is not None:
+            # self-play: GAE, the statistics and the update see the learner's rows alone
+            self._select_learner_rows()
+            b = b.learner
         if self.gae_impl is gae and b.gae_scratch is None:
             b.gae_scratch = gae_scratch(b.N * b.A, self.device)
-        self.gae_impl(b.rewards, b.values, b.dones, c.gamma, c.lam, b.adv, b.ret, b.adv_sums, self.env.n_agents,
+        self.gae_impl(b.rewards, b.values, b.dones, c.gamma, c.lam, b.adv, b.ret, b.adv_sums, b.A,
                       scratch=b.gae_scratch)
         stats = b.adv_stats  # (b.adv_sums is its first two entries)
         if self.collectives:
@@ -842,7 +1090,8 @@ class PPOTrainer:
             b.adv.sub_(mean.float()).div_(var.sqrt().float() + 1e-8)
 
     def _update_fused(self):
-        b, c = self.buf, self.cfg
+        full, c = self.buf, self.cfg
+        b = full if full.learner is None else full.learner  # self-play: the learner's dense rows
         assert c.horizon % c.minibatches == 0, 'fused update: horizon must split into whole time chunks'
         tc = c.horizon // c.minibatches
         params = list(self.policy.parameters())
@@ -872,14 +1121,15 @@ class PPOTrainer:
         self.last_stats = {'loss': loss.detach(), 'pg': pg.detach(), 'v': vl.detach(), 'entropy': ent.detach(),
                            'clipfrac': cf.detach()}
         if self.x_obs:
-            b.xb[0].copy_(b.xb[c.horizon])
+            full.xb[0].copy_(full.xb[c.horizon])
         else:
-            b.obs[0].copy_(b.obs[c.horizon])
+            full.obs[0].copy_(full.obs[c.horizon])
 
     def update(self):
         if self.fused is not None:
             return self._update_fused()
-        b, c = self.buf, self.cfg
+        full, c = self.buf, self.cfg
+        b = full if full.learner is None else full.learner  # self-play: the learner's dense rows
         M = c.horizon * b.N * b.A
         obs = b.obs[:c.horizon].reshape(M, b.D)
         acts = b.actions.reshape(M, 6)
@@ -905,7 +1155,7 @@ class PPOTrainer:
                 self.opt.step()
         self.last_stats = {'loss': loss.detach(), 'pg': pg.detach(), 'v': vl.detach()}
         self._sync_rollout_policy()
-        b.obs[0].copy_(b.obs[c.horizon])
+        full.obs[0].copy_(full.obs[c.horizon])
 
     # -- checkpoint / resume ------------------------------------------------
     # The reference has no trainer (SURVEY.md §5 lists checkpointing as an
@@ -921,6 +1171,12 @@ class PPOTrainer:
               'gen': self.gen.get_state(), 'obs0': self.buf.obs[0].detach().clone()}
         if self.x_obs:
             sd['xb0'] = self.buf.xb[0].detach().clone()  # (x_obs: the next rollout's rows; obs0 is the reset's)
+        if self.learner_agents is not None:
+            # self-play: 'policy' stays the learner (match.load_policy reads it as any checkpoint's)
+            sd['learner_agents'] = [int(a) for a in self.learner_agents]
+            sd['iterations'] = int(self.iterations)
+            if self.opponent is not None:
+                sd['opponent'] = {k: v.detach().clone() for k, v in self.opponent.state_dict().items()}
         if hasattr(self.env, 'get_state'):
             sd['env'] = self.env.get_state().detach().clone()
             if hasattr(self.env, 'state_meta'):
@@ -932,6 +1188,16 @@ class PPOTrainer:
 
     @torch.no_grad()
     def load_state_dict(self, sd):
+        have = sd.get('learner_agents')
+        if (None if have is None else [int(a) for a in have]) != self.learner_agents:
+            raise ValueError(f'checkpoint learner_agents {have} differ from this trainer\'s {self.learner_agents}')
+        if ('opponent' in sd) != (self.opponent is not None):
+            raise ValueError('checkpoint and trainer disagree on having an opponent')
+        if self.opponent is not None:
+            self.opponent.load_state_dict(sd['opponent'])
+            if self.opp_fused is not None:
+                self.opp_fused.pack()
+        self.iterations = int(sd.get('iterations', 0))
         self.policy.load_state_dict(sd['policy'])
         self.opt.load_state_dict(sd['opt'])
         if self.fused_opt is not None:
@@ -976,3 +1242,7 @@ class PPOTrainer:
             self.finish_rollout()
         with _phase('mas.update'):
             self.update()
+        self.iterations += 1
+        k = int(self.cfg.opponent_sync_every)
+        if self.opponent is not None and k > 0 and self.iterations % k == 0:
+            self.sync_opponent()

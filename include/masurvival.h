@@ -292,6 +292,35 @@ int mas_policy_act_sel(const void* packed, int32_t obs_dim, int64_t n_envs, int3
                        uint32_t agent_mask, int64_t first_row, const void* x_bf16, int64_t x_stride,
                        uint64_t seed, uint64_t step, int32_t greedy,
                        int8_t* actions, float* logp, float* value, float* logits_out, void* stream);
+/* mas_rows_select (an addition within ABI version 3): gather the rows of the
+ * selected agents of n_envs whole envs (row = env * n_agents + agent; bit a of
+ * agent_mask selects agent a, as for mas_policy_act_sel) into dense arrays of
+ * n_envs * popcount(agent_mask) rows, in (env, ascending agent) order: output
+ * row j is input row (j / m) * n_agents + (the (j % m)-th set bit of the
+ * mask), m = popcount(agent_mask).  What lets a trainer that owns only some
+ * agents run GAE and the mas_policy_train / mas_policy_dw kernels on its rows alone
+ * (time steps fold into n_envs: a [T][N][A] rollout is T * N envs).
+ * Every array pair is optional (NULL in and out together skips it); a pair
+ * with one NULL is an error.  x: columns [0, x_cols) of each selected row are
+ * copied bit for bit as 16-B chunks, the other columns of x_out are not
+ * written.  actions: 6 bytes per row.  f32_in / f32_out: HOST arrays of
+ * n_f32 <= 4 DEVICE pointers, [rows] fp32 each, read on the host and passed to
+ * the kernel by value.  Rows of unselected agents are never read and nothing
+ * past output row n_envs * m is written.  One launch serves all the arrays;
+ * the call is stream-ordered, allocates nothing and does not synchronise.
+ * MAS_ERR_INVALID_ARG, before any device work: n_agents outside 1..32, a zero
+ * agent_mask, a mask bit at or above n_agents, n_envs < 0 (or so large that a
+ * byte offset passes 2^63), n_f32 outside 0..4, a half-NULL pair, x_cols not
+ * a positive multiple of 8 or larger than either stride, a stride that is not
+ * a multiple of 8, x pointers not 16-B aligned (actions 2-B, fp32 4-B), an
+ * output pointer equal to its input.  n_envs == 0, or every pair NULL, is
+ * MAS_OK and launches nothing. */
+int mas_rows_select(int64_t n_envs, int32_t n_agents, uint32_t agent_mask,
+                    const void* x_bf16, int64_t x_stride,      /* [rows][x_stride] bf16 */
+                    void* x_out, int64_t x_out_stride, int32_t x_cols,
+                    const int8_t* actions, int8_t* actions_out, /* [rows][6] */
+                    int32_t n_f32, const float* const* f32_in, float* const* f32_out,
+                    void* stream);
 int mas_policy_train(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
                      const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
                      float vf_coef, float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
