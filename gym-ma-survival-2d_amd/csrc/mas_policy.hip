@@ -712,10 +712,6 @@ struct TrainArgs {
 // two consecutive rows of one feature as a 4-B word (half the store
 // instructions of 2-B stores, full 128-B segments per wave half).  Needs M even
 // (then both rows of a pair are in range or neither is).
-// MAS_POL_PAIR: rows per lane of the feature-major stores when M allows (1, 2, 4)
-#ifndef MAS_POL_PAIR
-#define MAS_POL_PAIR 2
-#endif
 // waves per SIMD of the train kernel (A/B: 1 = 512 registers, no spills)
 #ifndef MAS_POL_OCC
 #define MAS_POL_OCC 2
@@ -757,39 +753,6 @@ __device__ __forceinline__ void store_rows2(__bf16* base, int64_t M, int64_t row
     }
 }
 
-// Same with four consecutive rows per lane (8-B stores): a 4 x 4 transpose of
-// bf16 within each lane quad (rows r..r+3 x features crow(4g..4g+3)) in two
-// DPP exchanges, after which lane q of the quad holds feature 4g + q of all
-// four rows.  Needs M % 4 == 0.
-__device__ __forceinline__ void store_rows4(__bf16* base, int64_t M, int64_t row, int mt, int h, const bf8 (&v)[2])
-{
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    const int q = (int)(row & 3);
-    const bool hi = q & 2, odd = q & 1;
-    const u4 w[2] = {__builtin_bit_cast(u4, v[0]), __builtin_bit_cast(u4, v[1])};
-    uint2* dst = reinterpret_cast<uint2*>(base + (row & ~(int64_t)3));
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const uint32_t W0 = w[g >> 1][2 * (g & 1)], W1 = w[g >> 1][2 * (g & 1) + 1];  // features 4g+0,1 / 4g+2,3
-        // quad_perm [2, 3, 0, 1]: rows q and q ^ 2 trade the feature pair the other keeps
-        const uint32_t r1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)(hi ? W0 : W1), 0x4E, 0xF, 0xF, false);
-        const uint32_t X = hi ? r1 : W0, Y = hi ? W1 : r1;  // rows (q & 1), (q & 1) + 2 of feature pair (q & 2)
-        const uint32_t s2 = odd ? ((X & 0xffffu) | (Y << 16)) : ((X >> 16) | (Y & 0xffff0000u));
-        // quad_perm [1, 0, 3, 2]: rows q and q ^ 1 trade halves
-        const uint32_t r2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)s2, 0xB1, 0xF, 0xF, false);
-        uint2 o;
-        if (odd) {
-            o.x = (r2 & 0xffffu) | (X & 0xffff0000u);
-            o.y = (r2 >> 16) | (Y & 0xffff0000u);
-        } else {
-            o.x = (X & 0xffffu) | (r2 << 16);
-            o.y = (Y & 0xffffu) | (r2 & 0xffff0000u);
-        }
-        const int64_t f = 32 * mt + 8 * g + 4 * h + q;  // crow(4g + q, h)
-        dst[(f * M) >> 2] = o;
-    }
-}
-
 // Row-major activation store (RM): lane (row, h) writes its M-tile fragment as
 // two 16-B chunks of its own row, at columns 32 mt + 8 h (registers 0..7) and
 // 32 mt + 16 + 8 h (registers 8..15).  No lane exchange: stored column
@@ -806,6 +769,127 @@ __device__ __forceinline__ void store_rm(__bf16* base, int64_t ldr, int64_t row,
     bf8* p = reinterpret_cast<bf8*>(base + row * ldr + 32 * mt + 8 * h);
     p[0] = v[0];
     p[2] = v[1];
+}
+// Feature-major store of one row per lane (M or ld odd): 16 2-B stores
+__device__ __forceinline__ void store_rows1(__bf16* base, int64_t ld, int64_t row, int mt, int h, const bf8 (&v)[2])
+{
+#pragma unroll
+    for (int i = 0; i < 16; ++i) base[(int64_t)(32 * mt + crow(i, h)) * ld + row] = v[i >> 3][i & 7];
+}
+
+// ---------------------------------------------------------------------------
+// What the three train-kernel bodies (k_policy_train, train_cw_block,
+// k_policy_train_db) share.  They differ in how they stage weights and order
+// their memory operations, not in what a row computes: each loads the row's
+// loss inputs where its vmcnt order wants them and calls these.
+// ---------------------------------------------------------------------------
+// the row's six action bytes (w0: heads 0..3, w1: heads 4, 5), sign-extended
+__device__ __forceinline__ void act_decode(uint32_t w0, uint32_t w1, int (&a)[6])
+{
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a[k] = (int)(int8_t)(((k < 4 ? w0 : w1) >> (8 * (k & 3))) & 0xffu);
+}
+
+// The PPO loss gradient of one row (include/masurvival.h states the loss):
+// from the layer-3 accumulator z3 (the lane's 16 outputs before the bias b3:
+// a global, constant-address-space or LDS pointer), the row's six actions
+// and its advantage, old log-prob and return, the gradient dz[16] with
+// respect to the 15 logits and the value, and the row's four loss terms t =
+// {-min(s1, s2), (v - ret)^2, entropy, clipped ? 1 : 0}, which the caller
+// assigns or adds to its partials.  Pure arithmetic: no memory operation but
+// the b3 reads.
+// (log-softmax and probabilities recomputed in the gradient loop from the
+// heads' lse: the same values as keeping lsm[15] and p[15] between the loops,
+// 30 fewer live registers -- the budget k_policy_train_db needs)
+template <class B3>
+__device__ __forceinline__ void ppo_row_grad(const TrainArgs& A, const f16v& z3, B3 b3, const int (&a)[6], float adv,
+                                             float old_lp, float ret, float (&dz)[kO], float (&t)[4])
+{
+    float z[kO];
+#pragma unroll
+    for (int o = 0; o < kO; ++o) z[o] = z3[o] + b3[o];
+    float lse[6], hent[6];
+    float lp = 0.0f, ent = 0.0f;
+#pragma unroll
+    for (int hd = 0; hd < 6; ++hd) {
+        const int n = kHeadN[hd], off = kHeadOff[hd];
+        float mx = z[off];
+#pragma unroll
+        for (int k = 1; k < n; ++k) mx = fmaxf(mx, z[off + k]);
+        float se = 0.0f;
+#pragma unroll
+        for (int k = 0; k < n; ++k) se += exp_fast(z[off + k] - mx);
+        lse[hd] = mx + log_fast(se);
+        float e = 0.0f;
+        const int ak = a[hd];
+#pragma unroll
+        for (int k = 0; k < n; ++k) {
+            const float lsm = z[off + k] - lse[hd];
+            const float p = exp_fast(lsm);
+            e -= p * lsm;
+            if (k == ak) lp += lsm;
+        }
+        hent[hd] = e;
+        ent += e;
+    }
+    const float ratio = exp_fast(lp - old_lp);
+    const float s1 = ratio * adv;
+    const float rc = fminf(fmaxf(ratio, 1.0f - A.clip), 1.0f + A.clip);
+    const float s2 = rc * adv;
+    // d(-min(s1, s2))/d lp: the surrogate is differentiable through s1 where
+    // it is the minimum (ties included: then s1 == s2 with the ratio inside
+    // the clip range)
+    const float glp = s1 <= s2 ? -s1 : 0.0f;
+    const float sc = A.scale;
+#pragma unroll
+    for (int hd = 0; hd < 6; ++hd) {
+        const int n = kHeadN[hd], off = kHeadOff[hd];
+        const int ak = a[hd];
+#pragma unroll
+        for (int k = 0; k < n; ++k) {
+            const float oh = k == ak ? 1.0f : 0.0f;
+            const float lsm = z[off + k] - lse[hd];
+            const float p = exp_fast(lsm);
+            dz[off + k] = sc * (glp * (oh - p) + A.ent_coef * p * (lsm + hent[hd]));
+        }
+    }
+    const float dv = z[kO - 1] - ret;
+    dz[kO - 1] = sc * A.vf_coef * 2.0f * dv;
+    t[0] = -fminf(s1, s2);
+    t[1] = dv * dv;
+    t[2] = ent;
+    t[3] = fabsf(ratio - 1.0f) > A.clip ? 1.0f : 0.0f;
+}
+
+// one M-tile of a backward activation gradient: g * tanh'(z) from the stored
+// activation hv, as the bf16 operand fragments of the next product
+__device__ __forceinline__ void dact_tile(const f16v& g, const bf8 (&hv)[2], bf8 (&d)[2])
+{
+#pragma unroll
+    for (int i = 0; i < 16; ++i) d[i >> 3][i & 7] = (__bf16)(g[i] * dtanh((float)hv[i >> 3][i & 7]));
+}
+
+// per-block loss partials of the 4-wave kernels (through the LDS stage, after
+// its last reader): A.partials[block][4] = the sums of st over the block
+__device__ __forceinline__ void block_partials(const TrainArgs& A, bf8* wl, const float (&st)[4])
+{
+    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(wl);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v = st[k];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (l == 0) red[wv * 4 + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        float v = 0.0f;
+#pragma unroll
+        for (int w = 0; w < kTWaves; ++w) v += red[w * 4 + threadIdx.x];
+        A.partials[(int64_t)blockIdx.x * 4 + threadIdx.x] = v;
+    }
 }
 
 template <int KS, bool OFF32, bool RM>
@@ -839,30 +923,27 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
         const f16v z3 = layers23<true>(S, F + Lo.w23(), FB + Lo.b2(), l, on, h1, h2);
         const bf8* wb = S(F + Lo.wbk(), kBk0 * 64);  // W3^T
         // feature-major activations for the weight gradients
-        // wave-uniform store mode: 4 rows per lane (M % 4 == 0), 2 rows (M even), 1 row
-        const int rows_per_lane = !MAS_POL_PAIR ? 1 : ((M | LD) & 3) == 0 ? MAS_POL_PAIR : ((M | LD) & 1) == 0 ? 2 : 1;
-        const bool pair = rows_per_lane > 1;
+        // wave-uniform store mode: 2 rows per lane (M and ld even), else 1 row
+        const bool pair = ((M | LD) & 1) == 0;
         auto store_rows = [&](__bf16* base, int t, const bf8 (&v)[2]) {
             if (RM) store_rm(base, base == A.h1 || base == A.h2 ? LD : kH, row, t, h, v);
-            else if (rows_per_lane == 4) store_rows4(base, LD, row, t, h, v);
-            else store_rows2<OFF32>(base, LD, row, t, h, v);
+            else if (pair) store_rows2<OFF32>(base, LD, row, t, h, v);
+            else store_rows1(base, LD, row, t, h, v);
         };
-        if (on && ok) {
-            if (RM || pair) {
+        // (the 16 tiles of h1 and h2 under one test of the mode: tested per
+        // call, the 128 pair stores fall into 16 blocks that the compiler
+        // lays out behind the kernel's end, 8 % on the kernel's time)
+        if (on && ok && (RM || pair)) {
 #pragma unroll
-                for (int mt = 0; mt < kMT; ++mt) {
-                    store_rows(A.h1, mt, h1[mt]);
-                    store_rows(A.h2, mt, h2[mt]);
-                }
-            } else {
+            for (int mt = 0; mt < kMT; ++mt) {
+                store_rows(A.h1, mt, h1[mt]);
+                store_rows(A.h2, mt, h2[mt]);
+            }
+        } else if (on && ok) {
 #pragma unroll
-                for (int mt = 0; mt < kMT; ++mt)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int64_t f = 32 * mt + crow(i, h);
-                        A.h1[f * LD + row] = h1[mt][i >> 3][i & 7];
-                        A.h2[f * LD + row] = h2[mt][i >> 3][i & 7];
-                    }
+            for (int mt = 0; mt < kMT; ++mt) {
+                store_rows1(A.h1, LD, row, mt, h, h1[mt]);
+                store_rows1(A.h2, LD, row, mt, h, h2[mt]);
             }
         }
         // PPO loss gradient of this row (lane half 0 holds the 16 outputs)
@@ -870,61 +951,12 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
 #pragma unroll
         for (int o = 0; o < kO; ++o) dz[o] = 0.0f;
         if (on && h == 0 && ok) {
-            float z[kO];
-            const float* b3 = FB + Lo.b3();
-#pragma unroll
-            for (int o = 0; o < kO; ++o) z[o] = z3[o] + b3[o];
-            const int8_t* a = A.act + row * 6;
-            float lsm[15], p[15], hent[6];
-            float lp = 0.0f, ent = 0.0f;
-#pragma unroll
-            for (int hd = 0; hd < 6; ++hd) {
-                const int n = kHeadN[hd], off = kHeadOff[hd];
-                float mx = z[off];
-#pragma unroll
-                for (int k = 1; k < n; ++k) mx = fmaxf(mx, z[off + k]);
-                float se = 0.0f;
-#pragma unroll
-                for (int k = 0; k < n; ++k) se += exp_fast(z[off + k] - mx);
-                const float lse = mx + log_fast(se);
-                float e = 0.0f;
-                const int ak = a[hd];
-#pragma unroll
-                for (int k = 0; k < n; ++k) {
-                    lsm[off + k] = z[off + k] - lse;
-                    p[off + k] = exp_fast(lsm[off + k]);
-                    e -= p[off + k] * lsm[off + k];
-                    if (k == ak) lp += lsm[off + k];
-                }
-                hent[hd] = e;
-                ent += e;
-            }
-            const float adv = A.adv[row];
-            const float ratio = exp_fast(lp - A.old_logp[row]);
-            const float s1 = ratio * adv;
-            const float rc = fminf(fmaxf(ratio, 1.0f - A.clip), 1.0f + A.clip);
-            const float s2 = rc * adv;
-            // d(-min(s1, s2))/d lp: the surrogate is differentiable through
-            // s1 where it is the minimum (ties included: then s1 == s2 with
-            // the ratio inside the clip range)
-            const float glp = s1 <= s2 ? -s1 : 0.0f;
-            const float sc = A.scale;
-#pragma unroll
-            for (int hd = 0; hd < 6; ++hd) {
-                const int n = kHeadN[hd], off = kHeadOff[hd];
-                const int ak = a[hd];
-#pragma unroll
-                for (int k = 0; k < n; ++k) {
-                    const float oh = k == ak ? 1.0f : 0.0f;
-                    dz[off + k] = sc * (glp * (oh - p[off + k]) + A.ent_coef * p[off + k] * (lsm[off + k] + hent[hd]));
-                }
-            }
-            const float dv = z[kO - 1] - A.ret[row];
-            dz[kO - 1] = sc * A.vf_coef * 2.0f * dv;
-            st[0] = -fminf(s1, s2);
-            st[1] = dv * dv;
-            st[2] = ent;
-            st[3] = fabsf(ratio - 1.0f) > A.clip ? 1.0f : 0.0f;
+            const int8_t* ab = A.act + row * 6;
+            int a[6];
+            act_decode((uint32_t)(uint8_t)ab[0] | ((uint32_t)(uint8_t)ab[1] << 8) | ((uint32_t)(uint8_t)ab[2] << 16) |
+                           ((uint32_t)(uint8_t)ab[3] << 24),
+                       (uint32_t)(uint8_t)ab[4] | ((uint32_t)(uint8_t)ab[5] << 8), a);
+            ppo_row_grad(A, z3, FB + Lo.b3(), a, A.adv[row], A.old_logp[row], A.ret[row], dz, st);
             if (!RM) {
 #pragma unroll
                 for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
@@ -946,19 +978,8 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
             f16v g = f16v{};
             g = mfma(W3T[(mo * 2) * 64], dzf[0], g);
             g = mfma(W3T[(mo * 2 + 1) * 64], dzf[1], g);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float hv = (float)h2[mo][i >> 3][i & 7];
-                da2[mo][i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
-            }
-            if (ok) {
-                if (RM || pair) {
-                    store_rows(A.da2, mo, da2[mo]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) A.da2[(int64_t)(32 * mo + crow(i, h)) * LD + row] = da2[mo][i >> 3][i & 7];
-                }
-            }
+            dact_tile(g, h2[mo], da2[mo]);
+            if (ok) store_rows(A.da2, mo, da2[mo]);
         }
         // dA1 = (W2^T dA2) * (1 - h1^2), by M-tile of layer 1
         const bf8* W2T = wb + l;
@@ -971,37 +992,12 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
             for (int kk = 0; kk < 16; ++kk) g = mfma(W2T[((mt % (kMT / 2)) * 16 + kk) * 64], da2[kk >> 1][kk & 1], g);
             if (ok) {
                 bf8 d1[2];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float hv = (float)h1[mt][i >> 3][i & 7];
-                    d1[i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
-                }
-                if (RM || pair) {
-                    store_rows(A.da1, mt, d1);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) A.da1[(int64_t)(32 * mt + crow(i, h)) * LD + row] = d1[i >> 3][i & 7];
-                }
+                dact_tile(g, h1[mt], d1);
+                store_rows(A.da1, mt, d1);
             }
         }
     }
-    // per-block loss partials (through the LDS stage, after its last reader)
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(wl);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float v = st[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (l == 0) red[wv * 4 + k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        float v = 0.0f;
-#pragma unroll
-        for (int w = 0; w < kTWaves; ++w) v += red[w * 4 + threadIdx.x];
-        A.partials[(int64_t)blockIdx.x * 4 + threadIdx.x] = v;
-    }
+    block_partials(A, wl, st);
 }
 
 
@@ -1132,58 +1128,9 @@ __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, cons
 #pragma unroll
         for (int o = 0; o < kO; ++o) dz[o] = 0.0f;
         if (on && h == 0 && ok) {
-            float z[kO];
-#pragma unroll
-            for (int o = 0; o < kO; ++o) z[o] = z3[o] + b3[o];
             int a[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) a[k] = (int)(int8_t)(((k < 2 ? a01 : k < 4 ? a23 : a45) >> (8 * (k & 1))) & 0xffu);
-            float lsm[15], p[15], hent[6];
-            float lp = 0.0f, ent = 0.0f;
-#pragma unroll
-            for (int hd = 0; hd < 6; ++hd) {
-                const int n = kHeadN[hd], off = kHeadOff[hd];
-                float mx = z[off];
-#pragma unroll
-                for (int k = 1; k < n; ++k) mx = fmaxf(mx, z[off + k]);
-                float se = 0.0f;
-#pragma unroll
-                for (int k = 0; k < n; ++k) se += exp_fast(z[off + k] - mx);
-                const float lse = mx + log_fast(se);
-                float e = 0.0f;
-                const int ak = a[hd];
-#pragma unroll
-                for (int k = 0; k < n; ++k) {
-                    lsm[off + k] = z[off + k] - lse;
-                    p[off + k] = exp_fast(lsm[off + k]);
-                    e -= p[off + k] * lsm[off + k];
-                    if (k == ak) lp += lsm[off + k];
-                }
-                hent[hd] = e;
-                ent += e;
-            }
-            const float ratio = exp_fast(lp - old_lp);
-            const float s1 = ratio * adv;
-            const float rc = fminf(fmaxf(ratio, 1.0f - A.clip), 1.0f + A.clip);
-            const float s2 = rc * adv;
-            const float glp = s1 <= s2 ? -s1 : 0.0f;
-            const float sc = A.scale;
-#pragma unroll
-            for (int hd = 0; hd < 6; ++hd) {
-                const int n = kHeadN[hd], off = kHeadOff[hd];
-                const int ak = a[hd];
-#pragma unroll
-                for (int k = 0; k < n; ++k) {
-                    const float oh = k == ak ? 1.0f : 0.0f;
-                    dz[off + k] = sc * (glp * (oh - p[off + k]) + A.ent_coef * p[off + k] * (lsm[off + k] + hent[hd]));
-                }
-            }
-            const float dv = z[kO - 1] - ret;
-            dz[kO - 1] = sc * A.vf_coef * 2.0f * dv;
-            st[0] = -fminf(s1, s2);
-            st[1] = dv * dv;
-            st[2] = ent;
-            st[3] = fabsf(ratio - 1.0f) > A.clip ? 1.0f : 0.0f;
+            act_decode(a01 | (a23 << 16), a45, a);
+            ppo_row_grad(A, z3, b3, a, adv, old_lp, ret, dz, st);
 #pragma unroll
             for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
         }
@@ -1198,11 +1145,7 @@ __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, cons
             f16v g = f16v{};
             g = mfma(W3T[(mo * 2) * 64], dzf[0], g);
             g = mfma(W3T[(mo * 2 + 1) * 64], dzf[1], g);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float hv = (float)h2[mo][i >> 3][i & 7];
-                da2[mo][i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
-            }
+            dact_tile(g, h2[mo], da2[mo]);
             if (on && mo < kMT - MAS_POL_CW_DEFER) st2(A.da2, mo, da2[mo]);
         }
         // dA1 = (W2^T dA2) * (1 - h1^2), by M-tile of layer 1, in two half
@@ -1233,11 +1176,7 @@ __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, cons
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) g = mfma(W2T[((mt % (kMT / 2)) * 16 + kk) * 64], da2[kk >> 1][kk & 1], g);
             bf8 d1[2];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float hv = (float)h1[mt][i >> 3][i & 7];
-                d1[i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
-            }
+            dact_tile(g, h1[mt], d1);
             if (mt >= kMT / 2 - MAS_POL_CW_DEFER1 && mt < kMT / 2) {
                 d1k[mt][0] = d1[0];
                 d1k[mt][1] = d1[1];
@@ -1254,30 +1193,12 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
     __shared__ bf8 wl[kLdsFrag];
     const float* FB = reinterpret_cast<const float*>(A.packed);
     const float* B1 = FB + Layout{A.ks1}.b1();
-    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float st[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if ((int64_t)(blockIdx.x + 1) * kTWaves * 32 <= A.M)  // block-uniform
         train_cw_block<KS, OFF32, true>(A, wl, B1, st);
     else
         train_cw_block<KS, OFF32, false>(A, wl, B1, st);
-
-    // per-block loss partials (through the LDS stage, after its last reader)
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(wl);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float v = st[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (l == 0) red[wv * 4 + k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        float v = 0.0f;
-#pragma unroll
-        for (int w = 0; w < kTWaves; ++w) v += red[w * 4 + threadIdx.x];
-        A.partials[(int64_t)blockIdx.x * 4 + threadIdx.x] = v;
-    }
+    block_partials(A, wl, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1562,62 +1483,12 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
 #pragma unroll
         for (int o = 0; o < kO; ++o) dz[o] = 0.0f;
         if (h == 0) {
-            float z[kO];
-#pragma unroll
-            for (int o = 0; o < kO; ++o) z[o] = z3[o] + b3[o];
             int a[6];
+            act_decode(aw0, aw1, a);
+            float t[4];
+            ppo_row_grad(A, z3, b3, a, adv, old_lp, ret, dz, t);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) a[k] = (int)(int8_t)(((k < 4 ? aw0 : aw1) >> (8 * (k & 3))) & 0xffu);
-            // (log-softmax and probabilities recomputed in the gradient loop
-            // from the heads' lse: the same values, 30 fewer live registers)
-            float lse[6], hent[6];
-            float lp = 0.0f, ent = 0.0f;
-#pragma unroll
-            for (int hd = 0; hd < 6; ++hd) {
-                const int n = kHeadN[hd], off = kHeadOff[hd];
-                float mx = z[off];
-#pragma unroll
-                for (int k = 1; k < n; ++k) mx = fmaxf(mx, z[off + k]);
-                float se = 0.0f;
-#pragma unroll
-                for (int k = 0; k < n; ++k) se += exp_fast(z[off + k] - mx);
-                lse[hd] = mx + log_fast(se);
-                float e = 0.0f;
-                const int ak = a[hd];
-#pragma unroll
-                for (int k = 0; k < n; ++k) {
-                    const float lsm = z[off + k] - lse[hd];
-                    const float p = exp_fast(lsm);
-                    e -= p * lsm;
-                    if (k == ak) lp += lsm;
-                }
-                hent[hd] = e;
-                ent += e;
-            }
-            const float ratio = exp_fast(lp - old_lp);
-            const float s1 = ratio * adv;
-            const float rc = fminf(fmaxf(ratio, 1.0f - A.clip), 1.0f + A.clip);
-            const float s2 = rc * adv;
-            const float glp = s1 <= s2 ? -s1 : 0.0f;
-            const float sc_ = A.scale;
-#pragma unroll
-            for (int hd = 0; hd < 6; ++hd) {
-                const int n = kHeadN[hd], off = kHeadOff[hd];
-                const int ak = a[hd];
-#pragma unroll
-                for (int k = 0; k < n; ++k) {
-                    const float oh = k == ak ? 1.0f : 0.0f;
-                    const float lsm = z[off + k] - lse[hd];
-                    const float p = exp_fast(lsm);
-                    dz[off + k] = sc_ * (glp * (oh - p) + A.ent_coef * p * (lsm + hent[hd]));
-                }
-            }
-            const float dv = z[kO - 1] - ret;
-            dz[kO - 1] = sc_ * A.vf_coef * 2.0f * dv;
-            st[0] += -fminf(s1, s2);
-            st[1] += dv * dv;
-            st[2] += ent;
-            st[3] += fabsf(ratio - 1.0f) > A.clip ? 1.0f : 0.0f;
+            for (int k = 0; k < 4; ++k) st[k] += t[k];
             if (!DW3) {
 #pragma unroll
                 for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
@@ -1631,11 +1502,7 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
             f16v g = f16v{};
             g = mfma(wb[(mo * 2) * 64 + l], dzf[0], g);
             g = mfma(wb[(mo * 2 + 1) * 64 + l], dzf[1], g);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float hv = (float)h2[mo][i >> 3][i & 7];
-                da2[mo][i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
-            }
+            dact_tile(g, h2[mo], da2[mo]);
             st2(A.da2, row, mo, h, da2[mo]);  // 64 stores
         };
         if (!DW3) {
@@ -1719,11 +1586,7 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
 #pragma unroll
                 for (int kk = 0; kk < 16; ++kk) g = mfma(W2T[(q * 16 + kk) * 64 + l], da2[kk >> 1][kk & 1], g);
                 bf8 d1[2];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float hv = (float)h1[mt][i >> 3][i & 7];
-                    d1[i >> 3][i & 7] = (__bf16)(g[i] * dtanh(hv));
-                }
+                dact_tile(g, h1[mt], d1);
                 st2(A.da1, row, mt, h, d1);  // 8 stores
             }
             ++sc;
