@@ -25,6 +25,7 @@ namespace mas {
 struct ClassInfo {
     int words, w_rng, w_has32, w_stats, w_cont, w_invdt, lds_bytes;
     int am, post_union;  // agent slots; k_post_lanes' LDS union bytes (the in-place reset's permutation scratch)
+    int w_alive;         // state word of the alive mask (StateWords<C>::alive)
 };
 #define MAS_DECLARE(NAME)                                                                                     \
     ClassInfo class_info_##NAME();                                                                          \
@@ -68,12 +69,13 @@ hipError_t rows_select(int64_t n_envs, int n_agents, uint32_t mask, const void* 
 hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
                         const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
                         float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
-                        int64_t ld, float* partials, hipStream_t s, bool rm);
+                        int64_t ld, float* partials, hipStream_t s, bool rm, const float* row_w = nullptr);
 bool policy_train_dw3_ok(int D, int64_t M, int64_t ld);
 hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
                             const int8_t* act, const float* old_logp, const float* adv, const float* ret, float clip,
                             float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
-                            float* partials, float* dw3_out, float* scratch, hipStream_t s);
+                            float* partials, float* dw3_out, float* scratch, hipStream_t s,
+                            const float* row_w = nullptr);
 int policy_rm_feature(int col);
 int64_t policy_adam_scratch();
 hipError_t policy_adam(int64_t n, float* p, const float* g, float* m, float* v, float grad_scale, float max_norm,
@@ -131,6 +133,17 @@ __global__ void k_stats(uint32_t* __restrict__ state, int64_t N, int w_stats, fl
     }
 }
 
+// mas_alive: one thread per (env, agent) row reads the env's alive mask (a
+// wave's reads fall into a few consecutive words) and writes the row's flag
+__global__ __launch_bounds__(256) void k_alive(const uint32_t* __restrict__ state, int64_t N, int A, int w_alive,
+                                               float* __restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N * A) return;
+    const int64_t e = r / A;
+    const int i = (int)(r - e * A);
+    out[r] = (state[state_index(w_alive, e, N)] >> i) & 1u ? 1.0f : 0.0f;
+}
 
 // generic Box2D b2PolygonShape::Set (weld, gift wrap, normals) for the cone
 Poly4 poly_set4(const V2* in)
@@ -975,6 +988,16 @@ int mas_flush_stats(mas_handle* h, float* stats, void* stream)
     return MAS_OK;
 }
 
+int mas_alive(mas_handle* h, float* alive, void* stream)
+{
+    if (!h || !alive) return fail(MAS_ERR_INVALID_ARG, "mas_alive: null argument");
+    const int64_t rows = h->N * h->P.A;
+    hipLaunchKernelGGL(k_alive, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h->state, h->N,
+                       h->P.A, h->ops.info.w_alive, alive);
+    HIP_TRY(hipGetLastError());
+    return MAS_OK;
+}
+
 int mas_render_view(mas_handle* h, int64_t env, float* out)
 {
     if (!h || !out || env < 0 || env >= h->N) return fail(MAS_ERR_INVALID_ARG, "mas_render_view: bad argument");
@@ -1340,6 +1363,46 @@ int mas_policy_train_dw3(const void* packed, int32_t obs_dim, int64_t n_rows, co
                                          "2^32 / 514, MAS_POL_DB and MAS_POL_DW3 not 0): use mas_policy_train_ld");
     HIP_TRY(policy_train_dw3(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
                              ent_coef, scale, h1, da1, da2, ld, partials, dw3_out, scratch, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int mas_policy_train_w(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
+                       const int8_t* actions, const float* old_logp, const float* adv, const float* ret,
+                       const float* row_w, float clip, float vf_coef, float ent_coef, float scale, void* h1, void* h2,
+                       void* da1, void* da2, void* dz, int64_t ld, float* partials, void* stream)
+{
+    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !h2 ||
+        !da1 || !da2 || !dz || !partials || ld < n_rows)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_w: bad argument");
+    if (!row_w || (reinterpret_cast<uintptr_t>(row_w) & 3))
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_w: row_w must be a non-null, 4-B aligned device array");
+    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_w: x must be 16-B aligned with a padded row stride");
+    HIP_TRY(policy_train(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
+                         ent_coef, scale, h1, h2, da1, da2, dz, ld, partials, (hipStream_t)stream, false, row_w));
+    return MAS_OK;
+}
+
+int mas_policy_train_dw3_w(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
+                           const int8_t* actions, const float* old_logp, const float* adv, const float* ret,
+                           const float* row_w, float clip, float vf_coef, float ent_coef, float scale, void* h1,
+                           void* da1, void* da2, int64_t ld, float* partials, float* dw3_out, float* scratch,
+                           void* stream)
+{
+    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !da1 ||
+        !da2 || !partials || !dw3_out || !scratch || ld < n_rows)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3_w: bad argument");
+    if (!row_w || (reinterpret_cast<uintptr_t>(row_w) & 3))
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3_w: row_w must be a non-null, 4-B aligned device array");
+    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3_w: x must be 16-B aligned with a padded row stride");
+    if (!policy_train_dw3_ok(obs_dim, n_rows, ld))
+        return fail(MAS_ERR_UNSUPPORTED, "mas_policy_train_dw3_w: needs the persistent train kernel on every row "
+                                         "(n_rows a multiple of 256, 129 <= obs_dim <= 160, ld even and at most "
+                                         "2^32 / 514, MAS_POL_DB and MAS_POL_DW3 not 0): use mas_policy_train_w");
+    HIP_TRY(policy_train_dw3(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
+                             ent_coef, scale, h1, da1, da2, ld, partials, dw3_out, scratch, (hipStream_t)stream,
+                             row_w));
     return MAS_OK;
 }
 

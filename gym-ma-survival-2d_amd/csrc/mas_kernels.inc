@@ -517,6 +517,7 @@ void launch_lidar(hipStream_t s, const Params& P, const uint32_t* st, int64_t N,
 struct ClassInfo {
     int words, w_rng, w_has32, w_stats, w_cont, w_invdt, lds_bytes;
     int am, post_union;  // agent slots; k_post_lanes' LDS union bytes (the in-place reset's permutation scratch)
+    int w_alive;         // state word of the alive mask (StateWords<C>::alive)
 };
 
 template <class C>
@@ -573,6 +574,7 @@ ClassInfo class_info()
         if (fc.cont_at != LY::cont) o.words = -1;
     }
     delete L;
+    o.w_alive = StateWords<C>::alive;  // (checked against the visit order above)
     o.lds_bytes = (int)sizeof(ResetLds<C>);
     return o;
 }

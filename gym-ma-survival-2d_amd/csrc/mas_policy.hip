@@ -704,6 +704,7 @@ struct TrainArgs {
     float* partials;        // [gridDim.x][4]: sum pg, sum (v-ret)^2, sum entropy, clipped count
     float* dw3;             // k_policy_train_db<.., DW3>: [gridDim.x][16 * 256 + 16] partial dW3, db3 records
     int64_t bpw;            // k_policy_train_db<.., DW3>: consecutive 256-row blocks per workgroup (0: grid-stride)
+    const float* row_w;     // [M] the RW instantiations' policy-loss weight of each row (>= 0); else unused
 };
 
 // Feature-major activation store of one 32-row M-tile fragment (16 features
@@ -801,9 +802,15 @@ __device__ __forceinline__ void act_decode(uint32_t w0, uint32_t w1, int (&a)[6]
 // (log-softmax and probabilities recomputed in the gradient loop from the
 // heads' lse: the same values as keeping lsm[15] and p[15] between the loops,
 // 30 fewer live registers -- the budget k_policy_train_db needs)
-template <class B3>
+// RW (mas_policy_train_w): the row's weight w >= 0 on the policy terms -- the
+// surrogate and the entropy bonus, so the 15 logit gradients and t[0], t[2],
+// t[3] -- and not on the value term (dz[15], t[1]).  w == 0 selects zero for
+// them rather than multiplying: the row's ratio may have overflowed, and
+// 0 * inf is NaN.  w == 1 gives the unweighted bits (scale * 1, 1 * x).
+// Without RW, w is not read and the code is what it was before the flag.
+template <bool RW = false, class B3>
 __device__ __forceinline__ void ppo_row_grad(const TrainArgs& A, const f16v& z3, B3 b3, const int (&a)[6], float adv,
-                                             float old_lp, float ret, float (&dz)[kO], float (&t)[4])
+                                             float old_lp, float ret, float w, float (&dz)[kO], float (&t)[4])
 {
     float z[kO];
 #pragma unroll
@@ -841,6 +848,8 @@ __device__ __forceinline__ void ppo_row_grad(const TrainArgs& A, const f16v& z3,
     // the clip range)
     const float glp = s1 <= s2 ? -s1 : 0.0f;
     const float sc = A.scale;
+    const bool live = !RW || w != 0.0f;
+    const float scw = RW ? sc * w : sc;
 #pragma unroll
     for (int hd = 0; hd < 6; ++hd) {
         const int n = kHeadN[hd], off = kHeadOff[hd];
@@ -850,7 +859,8 @@ __device__ __forceinline__ void ppo_row_grad(const TrainArgs& A, const f16v& z3,
             const float oh = k == ak ? 1.0f : 0.0f;
             const float lsm = z[off + k] - lse[hd];
             const float p = exp_fast(lsm);
-            dz[off + k] = sc * (glp * (oh - p) + A.ent_coef * p * (lsm + hent[hd]));
+            const float g = scw * (glp * (oh - p) + A.ent_coef * p * (lsm + hent[hd]));
+            dz[off + k] = live ? g : 0.0f;
         }
     }
     const float dv = z[kO - 1] - ret;
@@ -859,6 +869,11 @@ __device__ __forceinline__ void ppo_row_grad(const TrainArgs& A, const f16v& z3,
     t[1] = dv * dv;
     t[2] = ent;
     t[3] = fabsf(ratio - 1.0f) > A.clip ? 1.0f : 0.0f;
+    if (RW) {  // (not t[1], the value term)
+        t[0] = live ? w * t[0] : 0.0f;
+        t[2] = live ? w * t[2] : 0.0f;
+        t[3] = live ? w * t[3] : 0.0f;
+    }
 }
 
 // one M-tile of a backward activation gradient: g * tanh'(z) from the stored
@@ -892,7 +907,7 @@ __device__ __forceinline__ void block_partials(const TrainArgs& A, bf8* wl, cons
     }
 }
 
-template <int KS, bool OFF32, bool RM>
+template <int KS, bool OFF32, bool RM, bool RW = false>
 __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_policy_train(TrainArgs A)
 {
     const Layout Lo{A.ks1};
@@ -956,7 +971,8 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
             act_decode((uint32_t)(uint8_t)ab[0] | ((uint32_t)(uint8_t)ab[1] << 8) | ((uint32_t)(uint8_t)ab[2] << 16) |
                            ((uint32_t)(uint8_t)ab[3] << 24),
                        (uint32_t)(uint8_t)ab[4] | ((uint32_t)(uint8_t)ab[5] << 8), a);
-            ppo_row_grad(A, z3, FB + Lo.b3(), a, A.adv[row], A.old_logp[row], A.ret[row], dz, st);
+            ppo_row_grad<RW>(A, z3, FB + Lo.b3(), a, A.adv[row], A.old_logp[row], A.ret[row],
+                             RW ? A.row_w[row] : 1.0f, dz, st);
             if (!RM) {
 #pragma unroll
                 for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
@@ -1073,7 +1089,7 @@ __device__ __forceinline__ void stage_landed(bool issued)
 // one block's rows; FULL: every row of the block is in range (all blocks
 // but the last), so no store sits under a branch -- a path that skips stores
 // would leave the copies the newest operations and force vmcnt(0) waits
-template <int KS, bool OFF32, bool FULL>
+template <int KS, bool OFF32, bool FULL, bool RW>
 __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, const float* B1, float (&st)[4])
 {
     const Layout Lo{A.ks1};
@@ -1110,6 +1126,7 @@ __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, cons
         const uint16_t* ap = reinterpret_cast<const uint16_t*>(A.act + rl * 6);  // 2-byte aligned
         const uint32_t a01 = ap[0], a23 = ap[1], a45 = ap[2];
         const float adv = A.adv[rl], old_lp = A.old_logp[rl], ret = A.ret[rl];
+        const float rw = RW ? A.row_w[rl] : 1.0f;
         typedef const __attribute__((address_space(4))) float cfloat;
         const cfloat* b3 = (const cfloat*)(FB + Lo.b3());
         // W3^T; h1 and h2 go out behind its copies
@@ -1130,7 +1147,7 @@ __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, cons
         if (on && h == 0 && ok) {
             int a[6];
             act_decode(a01 | (a23 << 16), a45, a);
-            ppo_row_grad(A, z3, b3, a, adv, old_lp, ret, dz, st);
+            ppo_row_grad<RW>(A, z3, b3, a, adv, old_lp, ret, rw, dz, st);
 #pragma unroll
             for (int o = 0; o < kO; ++o) A.dz[(int64_t)o * LD + row] = (__bf16)dz[o];
         }
@@ -1187,7 +1204,7 @@ __device__ __forceinline__ void train_cw_block(const TrainArgs& A, bf8* wl, cons
     }
 }
 
-template <int KS, bool OFF32>
+template <int KS, bool OFF32, bool RW = false>
 __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_policy_train_cw(TrainArgs A)
 {
     __shared__ bf8 wl[kLdsFrag];
@@ -1195,9 +1212,9 @@ __global__ __launch_bounds__(64 * kTWaves, MAS_POL_OCC * 4 / kTWaves) void k_pol
     const float* B1 = FB + Layout{A.ks1}.b1();
     float st[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if ((int64_t)(blockIdx.x + 1) * kTWaves * 32 <= A.M)  // block-uniform
-        train_cw_block<KS, OFF32, true>(A, wl, B1, st);
+        train_cw_block<KS, OFF32, true, RW>(A, wl, B1, st);
     else
-        train_cw_block<KS, OFF32, false>(A, wl, B1, st);
+        train_cw_block<KS, OFF32, false, RW>(A, wl, B1, st);
     block_partials(A, wl, st);
 }
 
@@ -1316,7 +1333,7 @@ __device__ __forceinline__ bf8 tr_frag(const uint8_t* p)
     return __builtin_bit_cast(bf8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <int KS, bool OFF32, bool DW3 = false>
+template <int KS, bool OFF32, bool DW3 = false, bool RW = false>
 __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, int64_t nblk)
 {
     static_assert(KS > 0, "compile-time layer-1 depth");
@@ -1377,6 +1394,7 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         // the loss inputs of the row (read in phase E)
         uint32_t aw0 = 0, aw1 = 0;  // the row's 6 action bytes: 0..3, 4..5
         float adv = 0.0f, old_lp = 0.0f, ret = 0.0f;
+        float rw = 1.0f;  // RW: the row's policy-loss weight, loaded with them
         // ---- layer 1: NCH stages of up to kKc k-steps
         {
             f16v acc[kMT];
@@ -1434,6 +1452,7 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
                 adv = A.adv[row];
                 old_lp = A.old_logp[row];
                 ret = A.ret[row];
+                if (RW) rw = A.row_w[row];
                 // 32 stores: the first h2 half; DW3 (h2 is not stored): the second h1 half
 #pragma unroll
                 for (int mt = 0; mt < kMT / 2; ++mt) {
@@ -1465,7 +1484,10 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
         // and force a full vmcnt(0) at the next reuse of their registers)
         // (a memory clobber anchors it after the phase's LDS reads and stores)
         // (in-out operands: nothing derived from them is computed before)
-        asm volatile("" : "+v"(aw0), "+v"(aw1), "+v"(adv), "+v"(old_lp), "+v"(ret)::"memory");
+        // (RW: the weight among them -- one more uncounted load, one more
+        // register from phase D to E; the other instantiations keep their list)
+        if (RW) asm volatile("" : "+v"(aw0), "+v"(aw1), "+v"(adv), "+v"(old_lp), "+v"(ret), "+v"(rw)::"memory");
+        else asm volatile("" : "+v"(aw0), "+v"(aw1), "+v"(adv), "+v"(old_lp), "+v"(ret)::"memory");
         // ---- E: W3^T; the loss gradient, dA2
         // phase D: the 32 h2 stores after them (plus the loss-input loads, not
         // counted: the compiler may combine the six 2-B / 4-B loads into fewer
@@ -1486,7 +1508,7 @@ __global__ __launch_bounds__(64 * kDW, 1) void k_policy_train_db(TrainArgs A, in
             int a[6];
             act_decode(aw0, aw1, a);
             float t[4];
-            ppo_row_grad(A, z3, b3, a, adv, old_lp, ret, dz, t);
+            ppo_row_grad<RW>(A, z3, b3, a, adv, old_lp, ret, rw, dz, t);
 #pragma unroll
             for (int k = 0; k < 4; ++k) st[k] += t[k];
             if (!DW3) {
@@ -2074,6 +2096,7 @@ static pol::TrainArgs train_args(const void* packed, int D, int64_t M, const voi
     A.partials = partials;
     A.dw3 = dw3;
     A.bpw = 0;
+    A.row_w = nullptr;
     return A;
 }
 
@@ -2142,12 +2165,16 @@ bool policy_train_dw3_ok(int D, int64_t M, int64_t ld)
 hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
                             const int8_t* act, const float* old_logp, const float* adv, const float* ret, float clip,
                             float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
-                            float* partials, float* dw3_out, float* scratch, hipStream_t s)
+                            float* partials, float* dw3_out, float* scratch, hipStream_t s, const float* row_w)
 {
     pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
                                   scale, h1, nullptr, da1, da2, nullptr, ld, partials, scratch);
+    A.row_w = row_w;
     const int grid = dw3_grid(M, &A.bpw);
-    auto kd = A.ks1 == 10 ? pol::k_policy_train_db<10, true, true> : pol::k_policy_train_db<9, true, true>;
+    // row_w (mas_policy_train_dw3_w): the RW instantiations, the same grid
+    auto kd = row_w ? (A.ks1 == 10 ? pol::k_policy_train_db<10, true, true, true>
+                                   : pol::k_policy_train_db<9, true, true, true>)
+                    : (A.ks1 == 10 ? pol::k_policy_train_db<10, true, true> : pol::k_policy_train_db<9, true, true>);
     hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, M / pol::kDRows);
     const int64_t n = pol::kD3Rec;
     hipLaunchKernelGGL(pol::k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, grid, scratch, dw3_out);
@@ -2157,10 +2184,14 @@ hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb
 hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
                         const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
                         float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
-                        int64_t ld, float* partials, hipStream_t s, bool rm)
+                        int64_t ld, float* partials, hipStream_t s, bool rm, const float* row_w)
 {
-    const pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
-                                        scale, h1, h2, da1, da2, dz, ld, partials, nullptr);
+    pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
+                                  scale, h1, h2, da1, da2, dz, ld, partials, nullptr);
+    A.row_w = row_w;
+    // row_w (mas_policy_train_w; never with rm): the same dispatch over the RW
+    // instantiations of the same kernels
+    const bool rw = row_w != nullptr;
     const bool o32 = train_o32(ld);
     // the persistent double-buffered kernel for the full 256-row blocks of the
     // PPO update's store mode (feature-major, two rows per lane, 32-bit
@@ -2170,7 +2201,9 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
     if (!rm && train_db_ok(o32, A.ks1, M, ld)) {
         const int ncu = train_ncu();
         const int64_t grid = nfull < ncu ? nfull : ncu;
-        auto kd = A.ks1 == 10 ? pol::k_policy_train_db<10, true> : pol::k_policy_train_db<9, true>;
+        auto kd = rw ? (A.ks1 == 10 ? pol::k_policy_train_db<10, true, false, true>
+                                    : pol::k_policy_train_db<9, true, false, true>)
+                     : (A.ks1 == 10 ? pol::k_policy_train_db<10, true> : pol::k_policy_train_db<9, true>);
         hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, nfull);
         const int64_t r0 = nfull * pol::kDRows;
         if (r0 < M) {  // the partial last block: k_policy_train on offset buffers
@@ -2181,13 +2214,16 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
             T.old_logp = A.old_logp + r0;
             T.adv = A.adv + r0;
             T.ret = A.ret + r0;
+            if (rw) T.row_w = A.row_w + r0;
             T.h1 = A.h1 + r0;
             T.h2 = A.h2 + r0;
             T.da1 = A.da1 + r0;
             T.da2 = A.da2 + r0;
             T.dz = A.dz + r0;
             T.partials = A.partials + 2 * nfull * 4;
-            auto kt = A.ks1 == 10 ? pol::k_policy_train<10, true, false> : pol::k_policy_train<9, true, false>;
+            auto kt = rw ? (A.ks1 == 10 ? pol::k_policy_train<10, true, false, true>
+                                        : pol::k_policy_train<9, true, false, true>)
+                         : (A.ks1 == 10 ? pol::k_policy_train<10, true, false> : pol::k_policy_train<9, true, false>);
             hipLaunchKernelGGL(kt, dim3((unsigned)policy_blocks(T.M)), dim3(64 * pol::kTWaves), 0, s, T);
         }
         return hipGetLastError();
@@ -2198,11 +2234,18 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
     // those keep k_policy_train.  MAS_POL_CW=0: k_policy_train everywhere
     const char* cw = getenv("MAS_POL_CW");
     if (!rm && o32 && A.ks1 != 9 && ((M | ld) & 1) == 0 && !(cw && cw[0] == '0')) {
-        auto kc = A.ks1 == 10 ? pol::k_policy_train_cw<10, true> : pol::k_policy_train_cw<0, true>;
+        auto kc = rw ? (A.ks1 == 10 ? pol::k_policy_train_cw<10, true, true> : pol::k_policy_train_cw<0, true, true>)
+                     : (A.ks1 == 10 ? pol::k_policy_train_cw<10, true> : pol::k_policy_train_cw<0, true>);
         hipLaunchKernelGGL(kc, dim3((unsigned)policy_blocks(M)), dim3(64 * pol::kTWaves), 0, s, A);
         return hipGetLastError();
     }
-    auto k = rm ? (A.ks1 == 10 ? pol::k_policy_train<10, false, true>
+    auto k = rw ? (A.ks1 == 10 ? (o32 ? pol::k_policy_train<10, true, false, true>
+                                      : pol::k_policy_train<10, false, false, true>)
+                   : A.ks1 == 9 ? (o32 ? pol::k_policy_train<9, true, false, true>
+                                       : pol::k_policy_train<9, false, false, true>)
+                                : (o32 ? pol::k_policy_train<0, true, false, true>
+                                       : pol::k_policy_train<0, false, false, true>))
+           : rm ? (A.ks1 == 10 ? pol::k_policy_train<10, false, true>
                    : A.ks1 == 9 ? pol::k_policy_train<9, false, true> : pol::k_policy_train<0, false, true>)
            : A.ks1 == 10 ? (o32 ? pol::k_policy_train<10, true, false> : pol::k_policy_train<10, false, false>)
            : A.ks1 == 9 ? (o32 ? pol::k_policy_train<9, true, false> : pol::k_policy_train<9, false, false>)

@@ -59,6 +59,7 @@ SIGNATURES = {
     'mas_step_x': (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     'mas_step_x_supported': (c_int32, [c_void_p, c_int32]),
     'mas_flush_stats': (c_int32, [c_void_p, c_void_p, c_void_p]),
+    'mas_alive': (c_int32, [c_void_p, c_void_p, c_void_p]),
     'mas_state_bytes': (c_int64, [c_void_p]),
     'mas_get_state': (c_int32, [c_void_p, c_void_p, c_void_p]),
     'mas_set_state': (c_int32, [c_void_p, c_void_p, c_void_p]),
@@ -98,6 +99,12 @@ SIGNATURES = {
     'mas_policy_train_dw3': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                        c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
                              + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
+    'mas_policy_train_w': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                     ctypes.c_float] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
+    'mas_policy_train_dw3_w': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_float] + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
     'mas_policy_train_rm': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                       c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
                             + [c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
@@ -113,7 +120,8 @@ SIGNATURES = {
 }
 # additions within ABI version 3 that an older build of the library (an A/B
 # variant loaded through MAS_LIB) may lack; their callers test with hasattr
-OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel', 'mas_rows_select'}
+OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel', 'mas_rows_select', 'mas_alive', 'mas_policy_train_w',
+            'mas_policy_train_dw3_w'}
 
 MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 

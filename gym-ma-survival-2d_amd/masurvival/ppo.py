@@ -24,6 +24,19 @@ drives the agents the trained policy does not own.  Both act in one rollout
 the learner's rows are gathered once into dense buffers (``mas_rows_select``,
 ``RolloutBuffer.learner``), and GAE, the advantage statistics and the update
 run on those alone.
+
+Dead agents (``PPOConfig.mask_dead``): the env ignores a dead agent's actions
+until the episode ends, so its rows carry no policy signal.  With the flag on,
+``RolloutBuffer.active`` records ``env.alive()`` before every step, the
+advantages are normalised over the active rows, and each minibatch weights a
+row's surrogate and entropy terms by ``active * rows / sum(active)`` (zeros
+where a minibatch has no active row): ``pg``, ``entropy`` and ``clipfrac`` become
+means over the active rows.  The value loss stays a mean over all rows: a dead
+agent keeps receiving reward, and a live row's GAE bootstraps from the value of
+the next, possibly dead, row.  Multi-GPU: every rank normalises its minibatch by
+its own active count and the ranks' gradients are averaged as before, so a rank
+with few active rows weighs each of them more than a global normalisation
+would -- an approximation that costs no extra collective.
 """
 from __future__ import annotations
 
@@ -88,6 +101,9 @@ class PPOConfig:
     # self-play (PPOTrainer(opponent=...)): copy the learner's weights into the
     # opponent after every k-th iteration() (lagged self-play); 0 = never
     opponent_sync_every: int = 0
+    # weight the policy terms of the loss (surrogate, entropy) by the agents'
+    # alive flags (env.alive()), see the module docstring; off: every row alike
+    mask_dead: bool = False
 
 
 def _split_k(m: int, cap: int = int(os.environ.get('MAS_SPLITK_CAP', '128'))) -> int:
@@ -584,15 +600,25 @@ class FusedPolicy:
             return None
         return gw, gb
 
-    def grads(self, xb, actions, old_logp, adv, ret, cfg: 'PPOConfig', stats: bool = True):
+    def grads(self, xb, actions, old_logp, adv, ret, cfg: 'PPOConfig', stats: bool = True, row_w=None):
         """Sets .grad of the policy parameters to the gradient of the PPO loss
         (mean over the M rows) and returns (loss, pg, v, entropy, clipfrac);
         stats=False skips those reductions (the update keeps only the last
-        minibatch's) and returns None."""
+        minibatch's) and returns None.  row_w: fp32 [M] weights (>= 0) of the
+        rows' policy terms (include/masurvival.h mas_policy_train_w); pg,
+        entropy and clipfrac are then sum(w * term) / M."""
         M = xb.shape[0]
         assert xb.dtype == torch.bfloat16 and xb.shape[1] == self.Dx and xb.is_contiguous()
         for t in (actions, old_logp, adv, ret):
             assert t.is_contiguous()
+        if row_w is not None:
+            if self.layout == 'rm':
+                raise ValueError('row weights need the feature-major layout (MAS_POL_LAYOUT=fm): the row-major '
+                                 'train kernel has no weighted form')
+            if not hasattr(self.lib, 'mas_policy_train_w'):
+                raise MasError('the loaded library has no mas_policy_train_w')
+            assert row_w.dtype == torch.float32 and row_w.shape == (M,) and row_w.is_contiguous()
+            assert row_w.device == xb.device
         if self.layout == 'rm':
             return self._grads_rm(xb, actions, old_logp, adv, ret, cfg)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
@@ -601,20 +627,35 @@ class FusedPolicy:
         # layer 3 inside the train kernel (mas_policy_train_dw3: h2 and dz are
         # not stored) where the library takes the minibatch that way
         fused3 = False
-        if '3' in _DW_LAYERS and hasattr(self.lib, 'mas_policy_train_dw3'):
+        if '3' in _DW_LAYERS and hasattr(self.lib, 'mas_policy_train_dw3' if row_w is None
+                                         else 'mas_policy_train_dw3_w'):
             B = self._buffers(M)
             span3 = self._grad_span(l3.weight, l3.bias)
             scratch3, out3 = self._dw_buffers(16, M)
-            rc = self.lib.mas_policy_train_dw3(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                               ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
-                                               cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['da1']), ptr(B['da2']),
-                                               B['ld'], ptr(B['part']),
-                                               ptr(span3[0] if span3 is not None else out3), ptr(scratch3),
-                                               self._stream())
+            if row_w is not None:
+                rc = self.lib.mas_policy_train_dw3_w(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
+                                                     ptr(old_logp), ptr(adv), ptr(ret), ptr(row_w), cfg.clip,
+                                                     cfg.vf_coef, cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['da1']),
+                                                     ptr(B['da2']), B['ld'], ptr(B['part']),
+                                                     ptr(span3[0] if span3 is not None else out3), ptr(scratch3),
+                                                     self._stream())
+            else:
+                rc = self.lib.mas_policy_train_dw3(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
+                                                   ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
+                                                   cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['da1']), ptr(B['da2']),
+                                                   B['ld'], ptr(B['part']),
+                                                   ptr(span3[0] if span3 is not None else out3), ptr(scratch3),
+                                                   self._stream())
             if rc != MAS_ERR_UNSUPPORTED:  # refused (nothing written): the unfused path below
                 check(rc)
                 fused3 = True
-        if not fused3:
+        if not fused3 and row_w is not None:
+            B = self._buffers_l3(M)
+            check(self.lib.mas_policy_train_w(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
+                                              ptr(old_logp), ptr(adv), ptr(ret), ptr(row_w), cfg.clip, cfg.vf_coef,
+                                              cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['h2']), ptr(B['da1']),
+                                              ptr(B['da2']), ptr(B['dz']), B['ld'], ptr(B['part']), self._stream()))
+        elif not fused3:
             B = self._buffers_l3(M)
             check(self.lib.mas_policy_train_ld(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
                                                ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
@@ -654,15 +695,55 @@ class FusedPolicy:
         return pg + cfg.vf_coef * v - cfg.ent_coef * ent, pg, v, ent, clipfrac
 
 
-def policy_loss_reference(policy, x, actions, old_logp, adv, ret, cfg: 'PPOConfig'):
+def masked_mean(x, row_w=None):
+    """mean(x), or mean(w * x) over all rows where the rows with w == 0 do
+    not count whatever x holds there (inf, NaN): a selection, as the kernels'.
+    (The selection guards the value only: autograd through it still multiplies
+    the dropped branch's derivative by zero, so what x is computed from must
+    be finite there -- surrogate_terms.)"""
+    if row_w is None:
+        return x.mean()
+    return torch.where(row_w != 0, row_w * x, torch.zeros_like(x)).mean()
+
+
+def surrogate_terms(lp, old_logp, adv, clip, row_w=None):
+    """(clipped surrogate min(r A, clip(r) A) per row, ratio r).  With row_w
+    the rows with w == 0 take log-ratio 0 and advantage 0 before the
+    exponential, so that neither their value nor their derivative can be
+    inf or NaN whatever old_logp and adv hold there."""
+    d = lp - old_logp
+    if row_w is not None:
+        live = row_w != 0
+        d = torch.where(live, d, torch.zeros_like(d))
+        adv = torch.where(live, adv, torch.zeros_like(adv))
+    ratio = torch.exp(d)
+    return torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv), ratio
+
+
+def policy_loss_reference(policy, x, actions, old_logp, adv, ret, cfg: 'PPOConfig', row_w=None):
     """Plain torch fp32 restatement of the PPO loss the fused kernels
-    differentiate (the numerics tests' reference): x fp32 rows [M, D]."""
+    differentiate (the numerics tests' reference): x fp32 rows [M, D].
+    row_w: fp32 [M] weights of the rows' surrogate and entropy terms
+    (mas_policy_train_w); the value term is never weighted."""
     logits, v = policy(x)
     lp, ent = evaluate_actions(logits, actions)
-    ratio = torch.exp(lp - old_logp)
-    pg = -torch.min(ratio * adv, ratio.clamp(1 - cfg.clip, 1 + cfg.clip) * adv).mean()
+    pg = masked_mean(-surrogate_terms(lp, old_logp, adv, cfg.clip, row_w)[0], row_w)
     vl = F.mse_loss(v, ret)
-    return pg + cfg.vf_coef * vl - cfg.ent_coef * ent.mean(), pg, vl, ent.mean()
+    em = masked_mean(ent, row_w)
+    return pg + cfg.vf_coef * vl - cfg.ent_coef * em, pg, vl, em
+
+
+def chunk_row_weights(active, chunks):
+    """(row_w shaped like active, share [chunks]) for `active` (fp32 0 / 1,
+    any shape) cut into `chunks` equal contiguous minibatches: row_w = active
+    * rows / sum(active) per chunk, zeros where a chunk has no active row (no
+    NaN); share = the chunk's fraction of active rows.  On the tensor's
+    device, no host synchronisation."""
+    a = active.reshape(chunks, -1)
+    rows = a.shape[1]
+    n = a.sum(1, dtype=torch.float64)
+    f = torch.where(n > 0, rows / n.clamp_min(1.0), torch.zeros_like(n)).float()
+    return (a * f.unsqueeze(1)).reshape(active.shape), (n / rows).float()
 
 
 class FusedAdam:
@@ -760,6 +841,16 @@ class RolloutBuffer:
         # iteration into a buffer of the same shape with A = its agent count
         # (alloc_learner); GAE and the update then read only that one
         self.learner = None
+        # PPOConfig.mask_dead (alloc_active): the agents' alive flags before
+        # each step, fp32 [T, N, A]; per iteration the minibatch weights made
+        # from them (chunk_row_weights) and each minibatch's active share
+        self.active = None
+        self.row_w = None
+        self.active_share = None
+
+    def alloc_active(self, device):
+        self.active = torch.ones((self.T, self.N, self.A), device=device, dtype=torch.float32)
+        return self.active
 
     def alloc_learner(self, m, device, fused=None):
         """The dense buffer of m learner agents per env: the fields GAE and the
@@ -769,6 +860,8 @@ class RolloutBuffer:
         lb.dones = self.dones
         if fused is not None:
             lb.xb = fused.x_buffer(self.T, self.N * m)
+        if self.active is not None:
+            lb.alloc_active(device)
         self.learner = lb
         return lb
 
@@ -819,6 +912,10 @@ class PPOTrainer:
         self.policy = PolicyMLP(env.obs_dim, cfg.hidden).to(self.device)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=cfg.lr, eps=1e-5)
         self.buf = RolloutBuffer(cfg.horizon, env.n_envs, env.n_agents, env.obs_dim, self.device)
+        if cfg.mask_dead:
+            if not callable(getattr(env, 'alive', None)):
+                raise ValueError(f'PPOConfig.mask_dead needs an env with alive() ({type(env).__name__} has none)')
+            self.buf.alloc_active(self.device)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed * 7919 + (dist.get_rank() if dist.is_initialized() else 0))
         self.buf.obs[0].copy_(env.reset())
@@ -852,6 +949,8 @@ class PPOTrainer:
             self._boot = (torch.empty((M, 6), dtype=torch.int8, device=self.device),
                           torch.empty((M,), dtype=torch.float32, device=self.device))
             self.fused.pack()
+            if cfg.mask_dead and self.fused.layout == 'rm':
+                raise ValueError('PPOConfig.mask_dead needs the feature-major update (MAS_POL_LAYOUT=fm)')
             if _FUSED_ADAM and FusedAdam.supports(self.opt):
                 self.fused_opt = FusedAdam(self.policy.parameters(), self.opt, self.fused.lib, self.device)
         else:
@@ -960,6 +1059,8 @@ class PPOTrainer:
         """One step with the learner on its agents and the opponent (when
         there is one) on the others: both fill the same actions[t]."""
         b = self.buf
+        if b.active is not None:
+            self.env.alive(out=b.active[t])
         if self.fused is not None:
             acts = b.actions[t].view(-1, 6)
             # one RNG key for both calls: it is keyed by the physical row
@@ -990,7 +1091,8 @@ class PPOTrainer:
             Dx = self.fused.Dx
             rows_select(b.A, self._lmask, x=b.xb[:T].view(-1, Dx), x_out=lb.xb.view(-1, Dx),
                         actions=b.actions.view(-1, 6), actions_out=lb.actions.view(-1, 6),
-                        f32=[(b.logp, lb.logp), (b.rewards, lb.rewards)])
+                        f32=[(b.logp, lb.logp), (b.rewards, lb.rewards)]
+                        + ([(b.active, lb.active)] if b.active is not None else []))
             rows_select(b.A, self._lmask, f32=[(b.values, lb.values)])  # T + 1 row blocks
             return
         i = self._lidx
@@ -999,6 +1101,8 @@ class PPOTrainer:
         lb.logp.copy_(b.logp.index_select(2, i))
         lb.rewards.copy_(b.rewards.index_select(2, i))
         lb.values.copy_(b.values.index_select(2, i))
+        if b.active is not None:
+            lb.active.copy_(b.active.index_select(2, i))
 
     @torch.no_grad()
     def rollout_step(self, t):
@@ -1014,6 +1118,8 @@ class PPOTrainer:
             for e, s, lo, hi in self.env.shard_slices():
                 with torch.cuda.stream(s):
                     r0, r1 = lo * A, hi * A
+                    if b.active is not None:
+                        e.alive(out=b.active[t][lo:hi])
                     if self.x_obs:
                         self.fused.act_x(b.xb[t][r0:r1], self.seed, self.steps_taken,
                                          b.actions[t].view(-1, 6)[r0:r1], b.logp[t].view(-1)[r0:r1],
@@ -1027,6 +1133,8 @@ class PPOTrainer:
             self.env.join()
             self.steps_taken += 1
             return
+        if b.active is not None:
+            self.env.alive(out=b.active[t])  # the agents whose actions this step reads
         if self.x_obs:
             # the env wrote these rows (bf16) at the last step; it writes the
             # next ones into row block t + 1
@@ -1078,8 +1186,19 @@ class PPOTrainer:
         self.gae_impl(b.rewards, b.values, b.dones, c.gamma, c.lam, b.adv, b.ret, b.adv_sums, b.A,
                       scratch=b.gae_scratch)
         stats = b.adv_stats  # (b.adv_sums is its first two entries)
+        if b.active is not None:
+            # the statistics over the active rows: (sum w adv, sum w adv^2, sum w) in double (w is 0 or 1);
+            # a rollout without any active row keeps a count of 1 (its weights are all zero anyway)
+            # (the reductions accumulate in double from the fp32 products: no fp64 copy of the rollout)
+            wa = b.active * b.adv
+            stats[0].copy_(wa.sum(dtype=torch.float64))
+            stats[1].copy_(torch.linalg.vector_norm(wa, 2, dtype=torch.float64).square())
+            stats[2].copy_(b.active.sum(dtype=torch.float64).clamp_min(1.0))
+            del wa
+            b.row_w, b.active_share = chunk_row_weights(b.active, c.minibatches if self.fused is not None else 1)
         if self.collectives:
-            stats[2].fill_(float(b.adv.numel()))  # the all-reduce below sums the counts in place
+            if b.active is None:
+                stats[2].fill_(float(b.adv.numel()))  # the all-reduce below sums the counts in place
             dist.all_reduce(stats, group=self.group)
         if self.gae_impl is gae and b.adv.is_cuda:
             # one launch (include/masurvival.h mas_adv_normalize), the roundings of the expression below
@@ -1103,10 +1222,12 @@ class PPOTrainer:
                 M = xb.shape[0]
                 # last_stats keeps the last minibatch's loss terms: only it reduces them
                 last = ep == c.epochs - 1 and n == c.minibatches - 1
+                rw = None if b.row_w is None else b.row_w[sl].reshape(M)
                 st = self.fused.grads(xb, b.actions[sl].reshape(M, 6), b.logp[sl].reshape(M),
-                                      b.adv[sl].reshape(M), b.ret[sl].reshape(M), c, stats=last)
+                                      b.adv[sl].reshape(M), b.ret[sl].reshape(M), c, stats=last, row_w=rw)
                 if last:
                     loss, pg, vl, ent, cf = st
+                    share = None if b.active_share is None else b.active_share[k]
                 if self.fused_opt is not None:
                     # flat gradient buffer: one all-reduce, the 1 / world folded into the step
                     if self.collectives:
@@ -1120,6 +1241,8 @@ class PPOTrainer:
                 self.fused.pack()
         self.last_stats = {'loss': loss.detach(), 'pg': pg.detach(), 'v': vl.detach(), 'entropy': ent.detach(),
                            'clipfrac': cf.detach()}
+        if share is not None:
+            self.last_stats['active'] = share
         if self.x_obs:
             full.xb[0].copy_(full.xb[c.horizon])
         else:
@@ -1136,17 +1259,18 @@ class PPOTrainer:
         old_lp, adv, ret = b.logp.reshape(M), b.adv.reshape(M), b.ret.reshape(M)
         params = list(self.policy.parameters())
         mb = M // c.minibatches
+        active = None if b.active is None else b.active.reshape(M)
         for _ in range(c.epochs):
             perm = torch.randperm(M, device=self.device, generator=self.gen)
             for k in range(c.minibatches):
                 idx = perm[k * mb:(k + 1) * mb]
                 logits, v = self._fwd(obs[idx])
                 lp, ent = evaluate_actions(logits, acts[idx])
-                ratio = torch.exp(lp - old_lp[idx])
-                a = adv[idx]
-                pg = -torch.min(ratio * a, ratio.clamp(1 - c.clip, 1 + c.clip) * a).mean()
+                # mask_dead: this minibatch's weights (its rows are a random draw: made here)
+                rw, share = (None, None) if active is None else chunk_row_weights(active[idx], 1)
+                pg = masked_mean(-surrogate_terms(lp, old_lp[idx], adv[idx], c.clip, rw)[0], rw)
                 vl = F.mse_loss(v, ret[idx])
-                loss = pg + c.vf_coef * vl - c.ent_coef * ent.mean()
+                loss = pg + c.vf_coef * vl - c.ent_coef * masked_mean(ent, rw)
                 self.opt.zero_grad(set_to_none=False)
                 loss.backward()
                 if self.collectives:
@@ -1154,6 +1278,8 @@ class PPOTrainer:
                 nn.utils.clip_grad_norm_(params, c.max_grad_norm)
                 self.opt.step()
         self.last_stats = {'loss': loss.detach(), 'pg': pg.detach(), 'v': vl.detach()}
+        if share is not None:
+            self.last_stats['active'] = share[0]
         self._sync_rollout_policy()
         full.obs[0].copy_(full.obs[c.horizon])
 

@@ -177,6 +177,23 @@ class VecMaSurvival:
         check(self._lib.mas_flush_stats(self._h, ctypes.c_void_p(s.data_ptr()), self._stream()))
         return s
 
+    def alive(self, out=None):
+        """fp32 [N, A] device tensor: 1.0 where the agent is alive in the state
+        the last observation describes, so where the next step reads its
+        action (mas_alive; stream-ordered, no synchronisation).  out: an
+        optional contiguous fp32 [N, A] tensor on this device to fill."""
+        torch = _torch()
+        if not hasattr(self._lib, 'mas_alive'):
+            raise RuntimeError('this build of the library has no mas_alive')
+        shp = (self.n_envs, self.n_agents)
+        if out is None:
+            out = torch.empty(shp, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shp or out.dtype != torch.float32 or not out.is_contiguous() or \
+                out.device != self.device:
+            raise ValueError(f'out must be a contiguous float32 {shp} tensor on {self.device}')
+        check(self._lib.mas_alive(self._h, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
     def split(self, flat):
         """View a [..., A, D] obs tensor as the reference's obs dict."""
         out = OrderedDict()
@@ -391,6 +408,23 @@ class ShardedVecMaSurvival:
         _torch().cuda.synchronize(self.device)
         d = [e.debug_counters() for e in self.envs]
         return {k: sum(x[k] for x in d) for k in d[0]}
+
+    def alive(self, out=None):
+        """As VecMaSurvival.alive over the shards, each filling its slice of
+        out on its own stream between fork() and join()."""
+        torch = _torch()
+        shp = (self.n_envs, self.n_agents)
+        if out is None:
+            out = torch.empty(shp, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shp or out.dtype != torch.float32 or not out.is_contiguous() or \
+                out.device != self.device:
+            raise ValueError(f'out must be a contiguous float32 {shp} tensor on {self.device}')
+        self.fork()
+        for e, s, lo, hi in self.shard_slices():
+            with torch.cuda.stream(s):
+                e.alive(out[lo:hi])
+        self.join()
+        return out
 
     def split(self, flat):
         return self.envs[0].split(flat)

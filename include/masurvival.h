@@ -155,6 +155,19 @@ int mas_step_x_supported(const mas_handle* h, int32_t auto_reset);
 #define MAS_STATS_WIDTH 19
 int mas_flush_stats(mas_handle* h, float* stats, void* stream);
 
+/* mas_alive (an addition within ABI version 3): which agents are alive, as
+ * DEVICE float alive[n_envs][n_agents] of 1.0f / 0.0f -- the env's alive
+ * mask, so the agents whose actions the next mas_step reads ("dead agents
+ * ignored" above).  It describes the state the last written observation rows
+ * describe: after an auto-reset step a reset env's agents are all alive.  An
+ * agent the zone killed in the last step, whose observation already shows
+ * health <= 0 but which acts once more before it is removed, counts as alive.
+ * fp32 because it is a loss weight (mas_policy_train_w) and mas_rows_select
+ * gathers fp32 arrays.  Stream-ordered, allocates nothing, does not
+ * synchronise, capturable.  MAS_ERR_INVALID_ARG for a null handle or output,
+ * before any device work. */
+int mas_alive(mas_handle* h, float* alive, void* stream);
+
 /* Raw SoA state image (checkpoint / parity state injection).  Byte size of
  * the image and copies to/from a caller DEVICE buffer of that size. */
 int64_t mas_state_bytes(const mas_handle* h);
@@ -352,6 +365,40 @@ int mas_policy_train_dw3(const void* packed, int32_t obs_dim, int64_t n_rows, co
                          const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
                          float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
                          float* partials, float* dw3_out, float* scratch, void* stream);
+/* mas_policy_train_w (an addition within ABI version 3): mas_policy_train_ld
+ * with a weight per row on the POLICY terms of the loss -- what lets a
+ * trainer mask the rows of dead agents (mas_alive), whose actions the env
+ * ignores.  row_w: DEVICE float [n_rows], 4-B aligned, values >= 0.  With
+ * w the row's weight, the row's gradient and loss terms are
+ *   dz[k]  = scale w (glp (onehot - p) + ent_coef p (logsoftmax + H_head))
+ *            for the 15 logits,
+ *   dz[15] = scale vf_coef 2 (v - ret)             (not weighted),
+ *   partials columns: w (-min(s1, s2)), (v - ret)^2, w entropy, w clipped.
+ * The value term stays on for every row: a dead agent still receives reward
+ * until the episode ends, and a live row's GAE bootstraps from the value of
+ * the next, possibly dead, row.  A row with w == 0 gives exactly zero (+-0)
+ * for its 15 logit gradients and its weighted loss terms whatever its other
+ * inputs are (a selection, not a product: its ratio may be inf); w == 1 on
+ * every row gives mas_policy_train_ld's outputs bit for bit.  The caller
+ * chooses the normalisation (the trainer: scale = 1 / n_rows and w = active
+ * n_rows / sum(active), so that the weighted columns sum to means over the
+ * active rows).  The kernels and their dispatch (and MAS_POL_DB, MAS_POL_CW,
+ * MAS_POL_FORCE_OFF64) are mas_policy_train_ld's; there is no row-major form.
+ * MAS_ERR_INVALID_ARG, before any device work: a null or misaligned row_w
+ * and whatever mas_policy_train_ld refuses.
+ * mas_policy_train_dw3_w: the same for mas_policy_train_dw3, with its
+ * conditions and its MAS_ERR_UNSUPPORTED (then: mas_policy_train_w +
+ * mas_policy_dw); compared with that pair as mas_policy_train_dw3 is with
+ * its own. */
+int mas_policy_train_w(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
+                       const int8_t* actions, const float* old_logp, const float* adv, const float* ret,
+                       const float* row_w, float clip, float vf_coef, float ent_coef, float scale, void* h1, void* h2,
+                       void* da1, void* da2, void* dz, int64_t ld, float* partials, void* stream);
+int mas_policy_train_dw3_w(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
+                           const int8_t* actions, const float* old_logp, const float* adv, const float* ret,
+                           const float* row_w, float clip, float vf_coef, float ent_coef, float scale, void* h1,
+                           void* da1, void* da2, int64_t ld, float* partials, float* dw3_out, float* scratch,
+                           void* stream);
 /* mas_policy_train_rm: the same kernel writing the activations ROW-major,
  * each lane storing its own row as 16-B chunks (no lane exchange):
  * h1, h2 [n_rows][ld_h] (ld_h >= 257, a multiple of 8; the caller keeps
