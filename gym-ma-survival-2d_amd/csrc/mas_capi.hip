@@ -14,6 +14,7 @@
 
 #include "../../include/masurvival.h"
 #include "mas_env.h"
+#include "mas_policy.h"  // fused policy MLP of the PPO consumer (mas_policy.hip)
 
 #ifndef MAS_CLASS_LIST
 #define MAS_CLASS_LIST "?"
@@ -51,38 +52,10 @@ MAS_DECLARE(xl)
 #ifdef MAS_HAVE_xxl
 MAS_DECLARE(xxl)
 #endif
-// fused policy MLP of the PPO consumer (mas_policy.hip)
-int64_t policy_packed_bytes(int D);
-int64_t policy_blocks(int64_t M);
-hipError_t policy_pack(int D, const float* W1, const float* b1, const float* W2, const float* b2, const float* W3,
-                       const float* b3, void* packed, hipStream_t s);
-hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, void* xb, int64_t xb_stride,
-                      uint64_t seed, uint64_t step, int64_t first_row, int8_t* act, float* logp, float* value,
-                      hipStream_t s);
-hipError_t policy_act_sel(const void* packed, int D, int64_t n_envs, int n_agents, uint32_t mask, const void* xb,
-                          int64_t xb_stride, uint64_t seed, uint64_t step, int64_t first_row, bool greedy,
-                          int8_t* act, float* logp, float* value, float* logits_out, hipStream_t s);
 // dense gather of the selected agents' rows (mas_select.hip)
 hipError_t rows_select(int64_t n_envs, int n_agents, uint32_t mask, const void* x, int64_t x_stride, void* x_out,
                        int64_t x_out_stride, int x_cols, const int8_t* act, int8_t* act_out, int n_f32,
                        const float* const* f_in, float* const* f_out, hipStream_t s);
-hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
-                        const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
-                        float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
-                        int64_t ld, float* partials, hipStream_t s, bool rm, const float* row_w = nullptr);
-bool policy_train_dw3_ok(int D, int64_t M, int64_t ld);
-hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
-                            const int8_t* act, const float* old_logp, const float* adv, const float* ret, float clip,
-                            float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
-                            float* partials, float* dw3_out, float* scratch, hipStream_t s,
-                            const float* row_w = nullptr);
-int policy_rm_feature(int col);
-int64_t policy_adam_scratch();
-hipError_t policy_adam(int64_t n, float* p, const float* g, float* m, float* v, float grad_scale, float max_norm,
-                       double lr, double b1, double b2, double eps, int64_t step, float* scratch, hipStream_t s);
-int64_t policy_dw_scratch(int F, int G, int64_t K);
-hipError_t policy_dw(int F, int G, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, float* out,
-                     float* scratch, hipStream_t s);
 }  // namespace mas
 
 namespace {
@@ -1203,6 +1176,13 @@ static bool policy_x_ok(int32_t obs_dim, int64_t x_stride)
 {
     return x_stride >= ((obs_dim + 15) / 16) * 16 && x_stride % 8 == 0;
 }
+static bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+// what the act entry points over bf16 rows ask of x, actions and (act_sel) logits_out
+static bool policy_act_x_ok(int32_t obs_dim, const void* x_bf16, int64_t x_stride, const int8_t* actions,
+                            const float* logits_out = nullptr)
+{
+    return policy_x_ok(obs_dim, x_stride) && aligned(x_bf16, 16) && aligned(actions, 2) && aligned(logits_out, 16);
+}
 
 int mas_policy_act_rows(const void* packed, int32_t obs_dim, int64_t n_rows, int64_t first_row, const float* obs,
                         void* x_bf16, int64_t x_stride, uint64_t seed, uint64_t step, int8_t* actions, float* logp,
@@ -1212,8 +1192,7 @@ int mas_policy_act_rows(const void* packed, int32_t obs_dim, int64_t n_rows, int
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act: bad argument");
     if (x_bf16 && !policy_x_ok(obs_dim, x_stride))
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act: x_stride must be a multiple of 8 >= 16*ceil(obs_dim/16)");
-    if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(actions) & 1) ||
-        (x_bf16 && (reinterpret_cast<uintptr_t>(x_bf16) & 15)))
+    if (!aligned(obs, 16) || !aligned(actions, 2) || !aligned(x_bf16, 16))
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act: misaligned buffer (obs/x 16 B, actions 2 B)");
     HIP_TRY(policy_act(packed, obs_dim, n_rows, obs, x_bf16, x_stride, seed, step, first_row, actions, logp, value,
                        (hipStream_t)stream));
@@ -1226,8 +1205,7 @@ int mas_policy_act_x(const void* packed, int32_t obs_dim, int64_t n_rows, int64_
 {
     if (!packed || obs_dim <= 0 || n_rows <= 0 || first_row < 0 || !x_bf16 || !actions || !logp || !value)
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_x: bad argument");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15) ||
-        (reinterpret_cast<uintptr_t>(actions) & 1))
+    if (!policy_act_x_ok(obs_dim, x_bf16, x_stride, actions))
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_x: x 16-B aligned with a padded row stride (a multiple "
                                          "of 8 >= 16*ceil(obs_dim/16)), actions 2-B aligned");
     HIP_TRY(policy_act(packed, obs_dim, n_rows, nullptr, const_cast<void*>(x_bf16), x_stride, seed, step, first_row,
@@ -1249,8 +1227,7 @@ int mas_policy_act_sel(const void* packed, int32_t obs_dim, int64_t n_envs, int3
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: bad argument (n_envs, obs_dim or first_row)");
     if (!packed || !x_bf16 || !actions || !logp || !value)
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: null packed, x_bf16, actions, logp or value");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15) ||
-        (reinterpret_cast<uintptr_t>(actions) & 1) || (reinterpret_cast<uintptr_t>(logits_out) & 15))
+    if (!policy_act_x_ok(obs_dim, x_bf16, x_stride, actions, logits_out))
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_act_sel: x 16-B aligned with a padded row stride (a multiple "
                                          "of 8 >= 16*ceil(obs_dim/16)), actions 2-B and logits_out 16-B aligned");
     if (n_envs == 0) return MAS_OK;
@@ -1317,19 +1294,42 @@ int mas_policy_act(const void* packed, int32_t obs_dim, int64_t n_rows, const fl
                                stream);
 }
 
+// The one argument check and launch of the six train entry points: `name`
+// goes in front of every message, the record's form says which fields the
+// call needs.  Every check before any HIP call.
+static int policy_train_call(const char* name, const TrainCall& c, void* stream)
+{
+    const bool rm = c.form == TrainForm::kRowMajor, dw3 = c.form == TrainForm::kDw3;
+    const auto bad = [name](int code, const char* what) { return fail(code, std::string(name) + ": " + what); };
+    if (!c.packed || c.D <= 0 || c.M <= 0 || !c.xb || !c.act || !c.old_logp || !c.adv || !c.ret || !c.h1 || !c.da1 ||
+        !c.da2 || !c.partials || (dw3 ? !c.dw3_out || !c.scratch : !c.h2 || !c.dz) ||
+        (rm ? c.ld < 257 || (c.ld % 8) != 0 : c.ld < c.M))
+        return bad(MAS_ERR_INVALID_ARG, rm ? "bad argument (ld_h >= 257, a multiple of 8)" : "bad argument");
+    if (c.weighted && (!c.row_w || !aligned(c.row_w, 4)))
+        return bad(MAS_ERR_INVALID_ARG, "row_w must be a non-null, 4-B aligned device array");
+    if (rm && !(aligned(c.h1, 16) && aligned(c.h2, 16) && aligned(c.da1, 16) && aligned(c.da2, 16) && aligned(c.dz, 16)))
+        return bad(MAS_ERR_INVALID_ARG, "activation buffers must be 16-B aligned");
+    if (!policy_x_ok(c.D, c.xb_stride) || !aligned(c.xb, 16))
+        return bad(MAS_ERR_INVALID_ARG, "x must be 16-B aligned with a padded row stride");
+    if (dw3 && !policy_train_dw3_ok(c.D, c.M, c.ld))
+        return fail(MAS_ERR_UNSUPPORTED, std::string(name) + ": needs the persistent train kernel on every row "
+                                         "(n_rows a multiple of 256, 129 <= obs_dim <= 160, ld even and at most "
+                                         "2^32 / 514, MAS_POL_DB and MAS_POL_DW3 not 0): use " +
+                                         (c.weighted ? "mas_policy_train_w" : "mas_policy_train_ld"));
+    HIP_TRY(policy_train(c, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+// Each entry point fills the record from its arguments, in TrainCall's field order.
+
 int mas_policy_train(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
                      const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
                      float vf_coef, float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
                      float* partials, void* stream)
 {
-    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !h2 ||
-        !da1 || !da2 || !dz || !partials)
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train: bad argument");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train: x must be 16-B aligned with a padded row stride");
-    HIP_TRY(policy_train(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
-                         ent_coef, scale, h1, h2, da1, da2, dz, n_rows, partials, (hipStream_t)stream, false));
-    return MAS_OK;
+    return policy_train_call(__func__, {TrainForm::kStored, false, packed, obs_dim, n_rows, x_bf16, x_stride, actions,
+                                  old_logp, adv, ret, nullptr, clip, vf_coef, ent_coef, scale, h1, h2, da1, da2, dz,
+                                  n_rows, partials, nullptr, nullptr}, stream);
 }
 
 int mas_policy_train_ld(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
@@ -1337,14 +1337,9 @@ int mas_policy_train_ld(const void* packed, int32_t obs_dim, int64_t n_rows, con
                         float vf_coef, float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
                         int64_t ld, float* partials, void* stream)
 {
-    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !h2 ||
-        !da1 || !da2 || !dz || !partials || ld < n_rows)
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_ld: bad argument");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_ld: x must be 16-B aligned with a padded row stride");
-    HIP_TRY(policy_train(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
-                         ent_coef, scale, h1, h2, da1, da2, dz, ld, partials, (hipStream_t)stream, false));
-    return MAS_OK;
+    return policy_train_call(__func__, {TrainForm::kStored, false, packed, obs_dim, n_rows, x_bf16, x_stride, actions,
+                                  old_logp, adv, ret, nullptr, clip, vf_coef, ent_coef, scale, h1, h2, da1, da2, dz, ld,
+                                  partials, nullptr, nullptr}, stream);
 }
 
 int mas_policy_train_dw3(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
@@ -1352,18 +1347,9 @@ int mas_policy_train_dw3(const void* packed, int32_t obs_dim, int64_t n_rows, co
                          float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
                          float* partials, float* dw3_out, float* scratch, void* stream)
 {
-    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !da1 ||
-        !da2 || !partials || !dw3_out || !scratch || ld < n_rows)
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3: bad argument");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3: x must be 16-B aligned with a padded row stride");
-    if (!policy_train_dw3_ok(obs_dim, n_rows, ld))
-        return fail(MAS_ERR_UNSUPPORTED, "mas_policy_train_dw3: needs the persistent train kernel on every row "
-                                         "(n_rows a multiple of 256, 129 <= obs_dim <= 160, ld even and at most "
-                                         "2^32 / 514, MAS_POL_DB and MAS_POL_DW3 not 0): use mas_policy_train_ld");
-    HIP_TRY(policy_train_dw3(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
-                             ent_coef, scale, h1, da1, da2, ld, partials, dw3_out, scratch, (hipStream_t)stream));
-    return MAS_OK;
+    return policy_train_call(__func__, {TrainForm::kDw3, false, packed, obs_dim, n_rows, x_bf16, x_stride, actions,
+                                  old_logp, adv, ret, nullptr, clip, vf_coef, ent_coef, scale, h1, nullptr, da1, da2,
+                                  nullptr, ld, partials, dw3_out, scratch}, stream);
 }
 
 int mas_policy_train_w(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
@@ -1371,16 +1357,9 @@ int mas_policy_train_w(const void* packed, int32_t obs_dim, int64_t n_rows, cons
                        const float* row_w, float clip, float vf_coef, float ent_coef, float scale, void* h1, void* h2,
                        void* da1, void* da2, void* dz, int64_t ld, float* partials, void* stream)
 {
-    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !h2 ||
-        !da1 || !da2 || !dz || !partials || ld < n_rows)
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_w: bad argument");
-    if (!row_w || (reinterpret_cast<uintptr_t>(row_w) & 3))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_w: row_w must be a non-null, 4-B aligned device array");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_w: x must be 16-B aligned with a padded row stride");
-    HIP_TRY(policy_train(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
-                         ent_coef, scale, h1, h2, da1, da2, dz, ld, partials, (hipStream_t)stream, false, row_w));
-    return MAS_OK;
+    return policy_train_call(__func__, {TrainForm::kStored, true, packed, obs_dim, n_rows, x_bf16, x_stride, actions,
+                                  old_logp, adv, ret, row_w, clip, vf_coef, ent_coef, scale, h1, h2, da1, da2, dz, ld,
+                                  partials, nullptr, nullptr}, stream);
 }
 
 int mas_policy_train_dw3_w(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
@@ -1389,21 +1368,9 @@ int mas_policy_train_dw3_w(const void* packed, int32_t obs_dim, int64_t n_rows, 
                            void* da1, void* da2, int64_t ld, float* partials, float* dw3_out, float* scratch,
                            void* stream)
 {
-    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !da1 ||
-        !da2 || !partials || !dw3_out || !scratch || ld < n_rows)
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3_w: bad argument");
-    if (!row_w || (reinterpret_cast<uintptr_t>(row_w) & 3))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3_w: row_w must be a non-null, 4-B aligned device array");
-    if (!policy_x_ok(obs_dim, x_stride) || (reinterpret_cast<uintptr_t>(x_bf16) & 15))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_dw3_w: x must be 16-B aligned with a padded row stride");
-    if (!policy_train_dw3_ok(obs_dim, n_rows, ld))
-        return fail(MAS_ERR_UNSUPPORTED, "mas_policy_train_dw3_w: needs the persistent train kernel on every row "
-                                         "(n_rows a multiple of 256, 129 <= obs_dim <= 160, ld even and at most "
-                                         "2^32 / 514, MAS_POL_DB and MAS_POL_DW3 not 0): use mas_policy_train_w");
-    HIP_TRY(policy_train_dw3(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
-                             ent_coef, scale, h1, da1, da2, ld, partials, dw3_out, scratch, (hipStream_t)stream,
-                             row_w));
-    return MAS_OK;
+    return policy_train_call(__func__, {TrainForm::kDw3, true, packed, obs_dim, n_rows, x_bf16, x_stride, actions,
+                                  old_logp, adv, ret, row_w, clip, vf_coef, ent_coef, scale, h1, nullptr, da1, da2,
+                                  nullptr, ld, partials, dw3_out, scratch}, stream);
 }
 
 int mas_policy_train_rm(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
@@ -1411,17 +1378,9 @@ int mas_policy_train_rm(const void* packed, int32_t obs_dim, int64_t n_rows, con
                         float vf_coef, float ent_coef, float scale, void* h1, void* h2, int64_t ld_h, void* da1,
                         void* da2, void* dz, float* partials, void* stream)
 {
-    const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!packed || obs_dim <= 0 || n_rows <= 0 || !x_bf16 || !actions || !old_logp || !adv || !ret || !h1 || !h2 ||
-        !da1 || !da2 || !dz || !partials || ld_h < 257 || (ld_h % 8) != 0)
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_rm: bad argument (ld_h >= 257, a multiple of 8)");
-    if (!al16(h1) || !al16(h2) || !al16(da1) || !al16(da2) || !al16(dz))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_rm: activation buffers must be 16-B aligned");
-    if (!policy_x_ok(obs_dim, x_stride) || !al16(x_bf16))
-        return fail(MAS_ERR_INVALID_ARG, "mas_policy_train_rm: x must be 16-B aligned with a padded row stride");
-    HIP_TRY(policy_train(packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp, adv, ret, clip, vf_coef,
-                         ent_coef, scale, h1, h2, da1, da2, dz, ld_h, partials, (hipStream_t)stream, true));
-    return MAS_OK;
+    return policy_train_call(__func__, {TrainForm::kRowMajor, false, packed, obs_dim, n_rows, x_bf16, x_stride, actions,
+                                  old_logp, adv, ret, nullptr, clip, vf_coef, ent_coef, scale, h1, h2, da1, da2, dz,
+                                  ld_h, partials, nullptr, nullptr}, stream);
 }
 
 int32_t mas_policy_rm_feature(int32_t col) { return col >= 0 && col < 256 ? policy_rm_feature(col) : -1; }
@@ -1448,10 +1407,9 @@ int64_t mas_policy_dw_scratch(int32_t f, int32_t g, int64_t k)
 int mas_policy_dw(int32_t f, int32_t g, int64_t k, const void* a, int64_t lda, const void* b, int64_t ldb, float* out,
                   float* scratch, void* stream)
 {
-    const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!(f == 16 || f == 256) || g != 256 || k <= 0 || (k % 32) != 0 || !a || !b || !out || !scratch)
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_dw: F in {16, 256}, G = 256, K a positive multiple of 32");
-    if (lda < k || ldb < k || (lda % 8) != 0 || (ldb % 8) != 0 || !al16(a) || !al16(b))
+    if (lda < k || ldb < k || (lda % 8) != 0 || (ldb % 8) != 0 || !aligned(a, 16) || !aligned(b, 16))
         return fail(MAS_ERR_INVALID_ARG, "mas_policy_dw: rows must be 16-B aligned (strides a multiple of 8)");
     HIP_TRY(policy_dw(f, g, k, a, lda, b, ldb, out, scratch, (hipStream_t)stream));
     return MAS_OK;

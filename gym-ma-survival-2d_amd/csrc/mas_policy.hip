@@ -37,6 +37,9 @@
 #include <cstdlib>
 
 #include <cstdint>
+#include <type_traits>
+
+#include "mas_policy.h"
 
 namespace mas {
 namespace pol {
@@ -2027,6 +2030,28 @@ hipError_t policy_adam(int64_t n, float* p, const float* g, float* m, float* v, 
 int64_t policy_blocks(int64_t M) { return (M + 32 * pol::kTWaves - 1) / (32 * pol::kTWaves); }
 static int64_t act_blocks(int64_t M) { return (M + 32 * pol::kWaves - 1) / (32 * pol::kWaves); }
 
+// Kernel selection, stated once per kernel family: pick<KS...>(ks1, f, flags...)
+// is f(ks, flags...) with every argument a compile-time constant
+// (std::integral_constant), so f names the instantiation in full, e.g.
+// [](auto ks, auto rw) { return &pol::k_policy_train_cw<ks, true, rw>; }.
+// ks is the first of KS... equal to ks1, else the last one listed (0: the
+// run-time layer-1 depth).  Every listed depth is instantiated with every
+// value of the flags, and nothing else is.
+template <int K0, int... KS, class F>
+static auto pick(int ks1, F f)
+{
+    if constexpr (sizeof...(KS) == 0)
+        return f(std::integral_constant<int, K0>{});
+    else
+        return ks1 == K0 ? f(std::integral_constant<int, K0>{}) : pick<KS...>(ks1, f);
+}
+template <int... KS, class F, class... B>
+static auto pick(int ks1, F f, bool flag, B... flags)
+{
+    return flag ? pick<KS...>(ks1, [f](auto ks, auto... c) { return f(ks, std::true_type{}, c...); }, flags...)
+                : pick<KS...>(ks1, [f](auto ks, auto... c) { return f(ks, std::false_type{}, c...); }, flags...);
+}
+
 hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, void* xb, int64_t xb_stride,
                       uint64_t seed, uint64_t step, int64_t first_row, int8_t* act, float* logp, float* value,
                       hipStream_t s)
@@ -2037,14 +2062,7 @@ hipError_t policy_act(const void* packed, int D, int64_t M, const float* obs, vo
     // the heads' sampling on both half-waves; MAS_ACT_SPLIT=0 (read per call): on one
     const char* sv = getenv("MAS_ACT_SPLIT");
     const bool split = !(sv && sv[0] == '0');
-    auto k = split ? (xin ? (ks1 == 10 ? pol::k_policy_act<10, true> : ks1 == 9 ? pol::k_policy_act<9, true>
-                                                                              : pol::k_policy_act<0, true>)
-                          : (ks1 == 10 ? pol::k_policy_act<10, false> : ks1 == 9 ? pol::k_policy_act<9, false>
-                                                                               : pol::k_policy_act<0, false>))
-                   : (xin ? (ks1 == 10 ? pol::k_policy_act<10, true, false> : ks1 == 9 ? pol::k_policy_act<9, true, false>
-                                                                              : pol::k_policy_act<0, true, false>)
-                          : (ks1 == 10 ? pol::k_policy_act<10, false, false>
-                                       : ks1 == 9 ? pol::k_policy_act<9, false, false> : pol::k_policy_act<0, false, false>));
+    auto k = pick<10, 9, 0>(ks1, [](auto ks, auto xi, auto sp) { return &pol::k_policy_act<ks, xi, sp>; }, xin, split);
     hipLaunchKernelGGL(k, dim3((unsigned)act_blocks(M)), dim3(64 * pol::kWaves), 0, s, (const uint8_t*)packed, D,
                        ks1, M, obs, (__bf16*)xb, xb_stride, seed, step, first_row, act, logp, value);
     return hipGetLastError();
@@ -2058,46 +2076,11 @@ hipError_t policy_act_sel(const void* packed, int D, int64_t n_envs, int n_agent
 {
     const int ks1 = (D + 15) / 16;
     const int m = __builtin_popcount(mask);
-    auto k = greedy ? (ks1 == 10 ? pol::k_policy_act_sel<10, true> : ks1 == 9 ? pol::k_policy_act_sel<9, true>
-                                                                               : pol::k_policy_act_sel<0, true>)
-                    : (ks1 == 10 ? pol::k_policy_act_sel<10, false> : ks1 == 9 ? pol::k_policy_act_sel<9, false>
-                                                                                : pol::k_policy_act_sel<0, false>);
+    auto k = pick<10, 9, 0>(ks1, [](auto ks, auto gr) { return &pol::k_policy_act_sel<ks, gr>; }, greedy);
     hipLaunchKernelGGL(k, dim3((unsigned)act_blocks(n_envs * m)), dim3(64 * pol::kWaves), 0, s,
                        (const uint8_t*)packed, ks1, n_envs, n_agents, mask, m, (const __bf16*)xb, xb_stride, seed,
                        step, first_row, act, logp, value, logits_out);
     return hipGetLastError();
-}
-
-static pol::TrainArgs train_args(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
-                                 const int8_t* act, const float* old_logp, const float* adv, const float* ret,
-                                 float clip, float vf_coef, float ent_coef, float scale, void* h1, void* h2,
-                                 void* da1, void* da2, void* dz, int64_t ld, float* partials, float* dw3)
-{
-    pol::TrainArgs A;
-    A.ld = ld;
-    A.packed = (const uint8_t*)packed;
-    A.ks1 = (D + 15) / 16;
-    A.M = M;
-    A.xb = (const __bf16*)xb;
-    A.xb_stride = xb_stride;
-    A.act = act;
-    A.old_logp = old_logp;
-    A.adv = adv;
-    A.ret = ret;
-    A.clip = clip;
-    A.vf_coef = vf_coef;
-    A.ent_coef = ent_coef;
-    A.scale = scale;
-    A.h1 = (__bf16*)h1;
-    A.h2 = (__bf16*)h2;
-    A.da1 = (__bf16*)da1;
-    A.da2 = (__bf16*)da2;
-    A.dz = (__bf16*)dz;
-    A.partials = partials;
-    A.dw3 = dw3;
-    A.bpw = 0;
-    A.row_w = nullptr;
-    return A;
 }
 
 // CUs of the current device: the persistent train kernel's workgroups
@@ -2155,55 +2138,43 @@ static int dw3_grid(int64_t M, int64_t* bpw)
 // and k_dw_reduce writes dw3_out [16 * 256 + 16].  Only where the persistent
 // kernel covers every row: its conditions and M % 256 == 0 (a partial last
 // block runs k_policy_train, which cannot accumulate); MAS_POL_DW3=0 (read
-// per call): never.  policy_train_dw3_ok false: nothing is launched or written.
+// per call): never.  policy_train_dw3_ok false: nothing is launched or written
+// (TrainForm::kDw3 of policy_train, below).
 bool policy_train_dw3_ok(int D, int64_t M, int64_t ld)
 {
     const char* e = getenv("MAS_POL_DW3");
     return train_db_ok(train_o32(ld), (D + 15) / 16, M, ld) && M % pol::kDRows == 0 && !(e && e[0] == '0');
 }
 
-hipError_t policy_train_dw3(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride,
-                            const int8_t* act, const float* old_logp, const float* adv, const float* ret, float clip,
-                            float vf_coef, float ent_coef, float scale, void* h1, void* da1, void* da2, int64_t ld,
-                            float* partials, float* dw3_out, float* scratch, hipStream_t s, const float* row_w)
+hipError_t policy_train(const TrainCall& c, hipStream_t s)
 {
-    pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
-                                  scale, h1, nullptr, da1, da2, nullptr, ld, partials, scratch);
-    A.row_w = row_w;
-    const int grid = dw3_grid(M, &A.bpw);
-    // row_w (mas_policy_train_dw3_w): the RW instantiations, the same grid
-    auto kd = row_w ? (A.ks1 == 10 ? pol::k_policy_train_db<10, true, true, true>
-                                   : pol::k_policy_train_db<9, true, true, true>)
-                    : (A.ks1 == 10 ? pol::k_policy_train_db<10, true, true> : pol::k_policy_train_db<9, true, true>);
-    hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, M / pol::kDRows);
-    const int64_t n = pol::kD3Rec;
-    hipLaunchKernelGGL(pol::k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, grid, scratch, dw3_out);
-    return hipGetLastError();
-}
-
-hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, int64_t xb_stride, const int8_t* act,
-                        const float* old_logp, const float* adv, const float* ret, float clip, float vf_coef,
-                        float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
-                        int64_t ld, float* partials, hipStream_t s, bool rm, const float* row_w)
-{
-    pol::TrainArgs A = train_args(packed, D, M, xb, xb_stride, act, old_logp, adv, ret, clip, vf_coef, ent_coef,
-                                  scale, h1, h2, da1, da2, dz, ld, partials, nullptr);
-    A.row_w = row_w;
-    // row_w (mas_policy_train_w; never with rm): the same dispatch over the RW
-    // instantiations of the same kernels
-    const bool rw = row_w != nullptr;
+    const int64_t M = c.M, ld = c.ld;
+    const int ks1 = (c.D + 15) / 16;
+    pol::TrainArgs A{(const uint8_t*)c.packed, ks1, M, (const __bf16*)c.xb, c.xb_stride, c.act, c.old_logp, c.adv,
+                     c.ret, c.clip, c.vf_coef, c.ent_coef, c.scale, (__bf16*)c.h1, (__bf16*)c.h2, (__bf16*)c.da1,
+                     (__bf16*)c.da2, (__bf16*)c.dz, ld, c.partials, /*dw3*/ c.scratch, /*bpw*/ 0, c.row_w};
+    // row_w (the _w entry points; never with rm): the same dispatch over the
+    // RW instantiations of the same kernels
+    const bool rw = c.row_w != nullptr, rm = c.form == TrainForm::kRowMajor;
+    const int64_t nfull = M / pol::kDRows;
+    if (c.form == TrainForm::kDw3) {  // policy_train_dw3_ok: the persistent kernel covers every row
+        const int grid = dw3_grid(M, &A.bpw);
+        auto kd = pick<10, 9>(ks1, [](auto ks, auto w) { return &pol::k_policy_train_db<ks, true, true, w>; }, rw);
+        hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, nfull);
+        const int64_t n = pol::kD3Rec;
+        hipLaunchKernelGGL(pol::k_dw_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, grid, c.scratch,
+                           c.dw3_out);
+        return hipGetLastError();
+    }
     const bool o32 = train_o32(ld);
     // the persistent double-buffered kernel for the full 256-row blocks of the
     // PPO update's store mode (feature-major, two rows per lane, 32-bit
     // offsets, compile-time layer-1 depth), k_policy_train for the rest;
     // MAS_POL_DB=0: k_policy_train_cw / k_policy_train only
-    const int64_t nfull = M / pol::kDRows;
-    if (!rm && train_db_ok(o32, A.ks1, M, ld)) {
+    if (!rm && train_db_ok(o32, ks1, M, ld)) {
         const int ncu = train_ncu();
         const int64_t grid = nfull < ncu ? nfull : ncu;
-        auto kd = rw ? (A.ks1 == 10 ? pol::k_policy_train_db<10, true, false, true>
-                                    : pol::k_policy_train_db<9, true, false, true>)
-                     : (A.ks1 == 10 ? pol::k_policy_train_db<10, true> : pol::k_policy_train_db<9, true>);
+        auto kd = pick<10, 9>(ks1, [](auto ks, auto w) { return &pol::k_policy_train_db<ks, true, false, w>; }, rw);
         hipLaunchKernelGGL(kd, dim3((unsigned)grid), dim3(64 * pol::kDW), 0, s, A, nfull);
         const int64_t r0 = nfull * pol::kDRows;
         if (r0 < M) {  // the partial last block: k_policy_train on offset buffers
@@ -2221,9 +2192,7 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
             T.da2 = A.da2 + r0;
             T.dz = A.dz + r0;
             T.partials = A.partials + 2 * nfull * 4;
-            auto kt = rw ? (A.ks1 == 10 ? pol::k_policy_train<10, true, false, true>
-                                        : pol::k_policy_train<9, true, false, true>)
-                         : (A.ks1 == 10 ? pol::k_policy_train<10, true, false> : pol::k_policy_train<9, true, false>);
+            auto kt = pick<10, 9>(ks1, [](auto ks, auto w) { return &pol::k_policy_train<ks, true, false, w>; }, rw);
             hipLaunchKernelGGL(kt, dim3((unsigned)policy_blocks(T.M)), dim3(64 * pol::kTWaves), 0, s, T);
         }
         return hipGetLastError();
@@ -2233,23 +2202,12 @@ hipError_t policy_train(const void* packed, int D, int64_t M, const void* xb, in
     // offset and 9-k-step layer-1 builds spill (compiler resource report), so
     // those keep k_policy_train.  MAS_POL_CW=0: k_policy_train everywhere
     const char* cw = getenv("MAS_POL_CW");
-    if (!rm && o32 && A.ks1 != 9 && ((M | ld) & 1) == 0 && !(cw && cw[0] == '0')) {
-        auto kc = rw ? (A.ks1 == 10 ? pol::k_policy_train_cw<10, true, true> : pol::k_policy_train_cw<0, true, true>)
-                     : (A.ks1 == 10 ? pol::k_policy_train_cw<10, true> : pol::k_policy_train_cw<0, true>);
-        hipLaunchKernelGGL(kc, dim3((unsigned)policy_blocks(M)), dim3(64 * pol::kTWaves), 0, s, A);
-        return hipGetLastError();
-    }
-    auto k = rw ? (A.ks1 == 10 ? (o32 ? pol::k_policy_train<10, true, false, true>
-                                      : pol::k_policy_train<10, false, false, true>)
-                   : A.ks1 == 9 ? (o32 ? pol::k_policy_train<9, true, false, true>
-                                       : pol::k_policy_train<9, false, false, true>)
-                                : (o32 ? pol::k_policy_train<0, true, false, true>
-                                       : pol::k_policy_train<0, false, false, true>))
-           : rm ? (A.ks1 == 10 ? pol::k_policy_train<10, false, true>
-                   : A.ks1 == 9 ? pol::k_policy_train<9, false, true> : pol::k_policy_train<0, false, true>)
-           : A.ks1 == 10 ? (o32 ? pol::k_policy_train<10, true, false> : pol::k_policy_train<10, false, false>)
-           : A.ks1 == 9 ? (o32 ? pol::k_policy_train<9, true, false> : pol::k_policy_train<9, false, false>)
-                        : (o32 ? pol::k_policy_train<0, true, false> : pol::k_policy_train<0, false, false>);
+    const bool use_cw = !rm && o32 && ks1 != 9 && ((M | ld) & 1) == 0 && !(cw && cw[0] == '0');
+    // rm: 64-bit offsets, no weighted form
+    auto k = use_cw ? pick<10, 0>(ks1, [](auto ks, auto w) { return &pol::k_policy_train_cw<ks, true, w>; }, rw)
+             : rm   ? pick<10, 9, 0>(ks1, [](auto ks) { return &pol::k_policy_train<ks, false, true>; })
+                    : pick<10, 9, 0>(ks1, [](auto ks, auto o, auto w) { return &pol::k_policy_train<ks, o, false, w>; },
+                                     o32, rw);
     hipLaunchKernelGGL(k, dim3((unsigned)policy_blocks(M)), dim3(64 * pol::kTWaves), 0, s, A);
     return hipGetLastError();
 }

@@ -47,6 +47,11 @@ class MasObsLayout(Structure):
     ]
 
 
+# what the six mas_policy_train* signatures share: packed, obs_dim, n_rows, x_bf16, x_stride, actions, old_logp,
+# adv, ret (then row_w in the _w forms), and clip, vf_coef, ent_coef, scale
+_TRAIN_HEAD = [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+_TRAIN_COEFS = [c_float] * 4
+
 # name -> (restype, argtypes); every symbol include/masurvival.h declares
 SIGNATURES = {
     'mas_create': (c_int32, [POINTER(MasConfig), c_int64, c_int32, POINTER(c_void_p)]),
@@ -90,24 +95,14 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     'mas_rows_select': (c_int32, [c_int64, c_int32, ctypes.c_uint32, c_void_p, c_int64, c_void_p, c_int64, c_int32,
                                   c_void_p, c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
-    'mas_policy_train': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
-                         + [c_void_p] * 7),
-    'mas_policy_train_ld': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
-                            + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
-    'mas_policy_train_dw3': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
-                             + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
-    'mas_policy_train_w': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                     ctypes.c_float] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
-    'mas_policy_train_dw3_w': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                         ctypes.c_float] + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
-    'mas_policy_train_rm': (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
-                            + [c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
+    'mas_policy_train': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p] * 7),
+    'mas_policy_train_ld': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
+    'mas_policy_train_dw3': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
+    'mas_policy_train_w': (c_int32, _TRAIN_HEAD + [c_void_p] + _TRAIN_COEFS + [c_void_p] * 5
+                           + [c_int64, c_void_p, c_void_p]),
+    'mas_policy_train_dw3_w': (c_int32, _TRAIN_HEAD + [c_void_p] + _TRAIN_COEFS + [c_void_p] * 3 + [c_int64]
+                               + [c_void_p] * 4),
+    'mas_policy_train_rm': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
     'mas_policy_rm_feature': (c_int32, [c_int32]),
     'mas_policy_adam_scratch': (c_int64, []),
     'mas_policy_adam': (c_int32, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, ctypes.c_float,

@@ -366,6 +366,11 @@ _ACT_PAD = int(os.environ.get('MAS_ACT_PAD', '64'))
 # row-sum GEMMs)
 _POL_LAYOUT = os.environ.get('MAS_POL_LAYOUT', 'fm')
 _RM_LDH = 264  # row stride of the row-major h1 / h2 (column 256: ones)
+# the train entry point of (form, row weights): layer 3 fused ('dw3'), stored
+# feature-major ('fm'), row-major ('rm': no weighted form)
+_TRAIN_FN = {('dw3', False): 'mas_policy_train_dw3', ('dw3', True): 'mas_policy_train_dw3_w',
+             ('fm', False): 'mas_policy_train_ld', ('fm', True): 'mas_policy_train_w',
+             ('rm', False): 'mas_policy_train_rm'}
 # MAS_FUSED_ADAM=0: the torch clip_grad_norm_ + Adam step in the fused trainer
 _FUSED_ADAM = os.environ.get('MAS_FUSED_ADAM', '1') != '0'
 
@@ -508,14 +513,39 @@ class FusedPolicy:
                           'part': torch.empty((nb, 4), dtype=torch.float32, device=self.device)}
         return self._bufs
 
+    def _train(self, form, xb, actions, old_logp, adv, ret, cfg, row_w, tail):
+        """One call of the train entry point of `form` (_TRAIN_FN): the head all
+        forms share, row_w where given, the coefficients, then the form's own
+        tail (tensors as their pointers).  Returns the library's return code."""
+        M = xb.shape[0]
+        args = [self.packed, self.D, M, xb, self.Dx, actions, old_logp, adv, ret]
+        args += ([row_w] if row_w is not None else []) + [cfg.clip, cfg.vf_coef, cfg.ent_coef, 1.0 / M, *tail]
+        fn = getattr(self.lib, _TRAIN_FN[form, row_w is not None])
+        return fn(*[ctypes.c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args], self._stream())
+
+    @staticmethod
+    def _set_grads(grads):
+        """.grad of every parameter in grads (None: already written in place)."""
+        for prm, g in grads.items():
+            if g is None:
+                continue
+            if prm.grad is None:
+                prm.grad = g.to(prm.dtype).clone(memory_format=torch.contiguous_format)
+            else:
+                prm.grad.copy_(g)
+
+    @staticmethod
+    def _loss_stats(part, M, cfg):
+        """(loss, pg, v, entropy, clipfrac) from the train kernel's partial records."""
+        s = part.sum(0) / M
+        pg, v, ent, clipfrac = s[0], s[1], s[2], s[3]
+        return pg + cfg.vf_coef * v - cfg.ent_coef * ent, pg, v, ent, clipfrac
+
     def _grads_rm(self, xb, actions, old_logp, adv, ret, cfg):
         M = xb.shape[0]
         B = self._buffers_rm(M)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        check(self.lib.mas_policy_train_rm(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                           ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef, cfg.ent_coef,
-                                           1.0 / M, ptr(B['h1']), ptr(B['h2']), _RM_LDH, ptr(B['da1']),
-                                           ptr(B['da2']), ptr(B['dz']), ptr(B['part']), self._stream()))
+        check(self._train('rm', xb, actions, old_logp, adv, ret, cfg, None,
+                          [B['h1'], B['h2'], _RM_LDH, B['da1'], B['da2'], B['dz'], B['part']]))
         q = self._rm_q
         g3 = _splitk_tn(B['dz'], B['h2'][:, :257])               # [16, 257], columns stored order
         g2 = _splitk_tn(B['da2'], B['h1'][:, :257])              # [256, 257]
@@ -523,17 +553,10 @@ class FusedPolicy:
         g2 = g2.index_select(0, q)
         p = self.policy
         l1, l2, l3 = p.body[0], p.body[2], p.head
-        grads = {l3.weight: g3[:, :256].index_select(1, q), l3.bias: g3[:, 256],
-                 l2.weight: g2[:, :256].index_select(1, q), l2.bias: g2[:, 256],
-                 l1.weight: g1.index_select(0, q)[:, :self.D], l1.bias: g1[:, self.D].index_select(0, q)}
-        for prm, g in grads.items():
-            if prm.grad is None:
-                prm.grad = g.to(prm.dtype).clone(memory_format=torch.contiguous_format)
-            else:
-                prm.grad.copy_(g)
-        s = B['part'].sum(0) / M
-        pg, v, ent, clipfrac = s[0], s[1], s[2], s[3]
-        return pg + cfg.vf_coef * v - cfg.ent_coef * ent, pg, v, ent, clipfrac
+        self._set_grads({l3.weight: g3[:, :256].index_select(1, q), l3.bias: g3[:, 256],
+                         l2.weight: g2[:, :256].index_select(1, q), l2.bias: g2[:, 256],
+                         l1.weight: g1.index_select(0, q)[:, :self.D], l1.bias: g1[:, self.D].index_select(0, q)})
+        return self._loss_stats(B['part'], M, cfg)
 
     def _buffers(self, M):
         if self._bufs is None or self._bufs['M'] != M:
@@ -621,46 +644,25 @@ class FusedPolicy:
             assert row_w.device == xb.device
         if self.layout == 'rm':
             return self._grads_rm(xb, actions, old_logp, adv, ret, cfg)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         p = self.policy
         l1, l2, l3 = p.body[0], p.body[2], p.head
         # layer 3 inside the train kernel (mas_policy_train_dw3: h2 and dz are
         # not stored) where the library takes the minibatch that way
         fused3 = False
-        if '3' in _DW_LAYERS and hasattr(self.lib, 'mas_policy_train_dw3' if row_w is None
-                                         else 'mas_policy_train_dw3_w'):
+        if '3' in _DW_LAYERS and hasattr(self.lib, _TRAIN_FN['dw3', row_w is not None]):
             B = self._buffers(M)
             span3 = self._grad_span(l3.weight, l3.bias)
             scratch3, out3 = self._dw_buffers(16, M)
-            if row_w is not None:
-                rc = self.lib.mas_policy_train_dw3_w(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                                     ptr(old_logp), ptr(adv), ptr(ret), ptr(row_w), cfg.clip,
-                                                     cfg.vf_coef, cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['da1']),
-                                                     ptr(B['da2']), B['ld'], ptr(B['part']),
-                                                     ptr(span3[0] if span3 is not None else out3), ptr(scratch3),
-                                                     self._stream())
-            else:
-                rc = self.lib.mas_policy_train_dw3(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                                   ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
-                                                   cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['da1']), ptr(B['da2']),
-                                                   B['ld'], ptr(B['part']),
-                                                   ptr(span3[0] if span3 is not None else out3), ptr(scratch3),
-                                                   self._stream())
+            rc = self._train('dw3', xb, actions, old_logp, adv, ret, cfg, row_w,
+                             [B['h1'], B['da1'], B['da2'], B['ld'], B['part'],
+                              span3[0] if span3 is not None else out3, scratch3])
             if rc != MAS_ERR_UNSUPPORTED:  # refused (nothing written): the unfused path below
                 check(rc)
                 fused3 = True
-        if not fused3 and row_w is not None:
+        if not fused3:
             B = self._buffers_l3(M)
-            check(self.lib.mas_policy_train_w(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                              ptr(old_logp), ptr(adv), ptr(ret), ptr(row_w), cfg.clip, cfg.vf_coef,
-                                              cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['h2']), ptr(B['da1']),
-                                              ptr(B['da2']), ptr(B['dz']), B['ld'], ptr(B['part']), self._stream()))
-        elif not fused3:
-            B = self._buffers_l3(M)
-            check(self.lib.mas_policy_train_ld(ptr(self.packed), self.D, M, ptr(xb), self.Dx, ptr(actions),
-                                               ptr(old_logp), ptr(adv), ptr(ret), cfg.clip, cfg.vf_coef,
-                                               cfg.ent_coef, 1.0 / M, ptr(B['h1']), ptr(B['h2']), ptr(B['da1']),
-                                               ptr(B['da2']), ptr(B['dz']), B['ld'], ptr(B['part']), self._stream()))
+            check(self._train('fm', xb, actions, old_logp, adv, ret, cfg, row_w,
+                              [B['h1'], B['h2'], B['da1'], B['da2'], B['dz'], B['ld'], B['part']]))
         B = {k: (v[:, :M] if k in ('h1', 'h2', 'da1', 'da2', 'dz') else v) for k, v in B.items()}
         # layers 2 / 3: the split-K MFMA kernel (mas_policy_dw) where enabled,
         # else the split-K GEMM over the ones-row trick; layer 1 reads x
@@ -679,20 +681,10 @@ class FusedPolicy:
             g2 = _splitk_nt(B['da2'], B['h1'])         # [256, 257]
             g2w, g2b = g2[:, :256], g2[:, 256]
         g1 = _splitk_nn(B['da1'], xb[:, :self.D + 1])  # [256, D + 1]
-        grads = {l3.weight: g3w, l3.bias: g3b, l2.weight: g2w, l2.bias: g2b,
-                 l1.weight: g1[:, :self.D], l1.bias: g1[:, self.D]}
-        for prm, g in grads.items():
-            if g is None:
-                continue  # written in place above
-            if prm.grad is None:
-                prm.grad = g.to(prm.dtype).clone(memory_format=torch.contiguous_format)
-            else:
-                prm.grad.copy_(g)
-        if not stats:
-            return None
-        s = B['part'].sum(0) / M
-        pg, v, ent, clipfrac = s[0], s[1], s[2], s[3]
-        return pg + cfg.vf_coef * v - cfg.ent_coef * ent, pg, v, ent, clipfrac
+        # (a None gradient: written in place above)
+        self._set_grads({l3.weight: g3w, l3.bias: g3b, l2.weight: g2w, l2.bias: g2b,
+                         l1.weight: g1[:, :self.D], l1.bias: g1[:, self.D]})
+        return self._loss_stats(B['part'], M, cfg) if stats else None
 
 
 def masked_mean(x, row_w=None):
