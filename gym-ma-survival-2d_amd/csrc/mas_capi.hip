@@ -436,7 +436,10 @@ __global__ __launch_bounds__(256) void k_sample(int64_t M, const float* __restri
         for (int k = 0; k < 3; ++k) {
             if (k >= n[h]) continue;
             const uint64_t r = mix64(base + (uint64_t)(h * 4 + k));
-            const float u = ((float)(r >> 40) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
+            // (0, 1]: x + 0.5f rounds to even for x >= 2^23, so x = 2^24 - 1 gives u = 1.0.
+            // Then -logf(u) = -0, logf(-0) = -inf and g = +inf: the option wins whatever the
+            // logits (2^-24 per draw), with a finite log-prob; no NaN arises (tests/sampler_ref.py)
+            const float u = ((float)(r >> 40) + 0.5f) * (1.0f / 16777216.0f);
             const float g = l[off + k] - logf(-logf(u));
             if (g > bv) { bv = g; best = k; }
         }

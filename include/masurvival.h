@@ -211,7 +211,24 @@ int mas_adv_normalize(int64_t n, float* adv, const double* stats, void* stream);
  * row: the heads' logits in order), Gumbel-max with a counter-based RNG keyed
  * by (seed, step, row); writes actions int8 [n_rows][6] and the log-prob of
  * the drawn actions float [n_rows].  Batched form of the reference's policy
- * act() (demo.py:14-22).  DEVICE pointers. */
+ * act() (demo.py:14-22).  DEVICE pointers.
+ *
+ * The stream, so that a host can reproduce a rollout's draws (uint64
+ * arithmetic that wraps; tests/sampler_ref.py restates it in numpy):
+ *   mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *             z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31
+ *             (SplitMix64's output function)
+ *   base = mix64(seed ^ mix64(step * 0x100000001B3 + row))
+ *   r    = mix64(base + 4 * head + option)     head 0..5, option 0..n_head-1
+ *   u    = ((float)(r >> 40) + 0.5f) * 2^-24   in fp32
+ * row is the row's index in the whole batch (first_row + the row of the call
+ * for the mas_policy_act_* forms).  r >> 40 < 2^24 converts exactly; the sum
+ * with 0.5f is exact below 2^23 and rounds to even above, so u lies in
+ * (0, 1]: r >> 40 = 0 gives 2^-25 and r >> 40 = 2^24 - 1 gives 1.0.  An
+ * option's score is logit - log(-log(u)) in fp32, and the head's action the
+ * first option with the greatest score (a strict > scan from option 0).
+ * u = 1.0 scores +inf: that option is drawn whatever the logits, once in 2^24
+ * draws, with a finite log-prob. */
 int mas_sample_actions(int64_t n_rows, const float* logits, int64_t row_stride, uint64_t seed, uint64_t step,
                        int8_t* actions, float* logp, void* stream);
 
