@@ -39,6 +39,25 @@ per row smaller than the rounding term, while the bound adds absolute
 values over the rows, so it holds for a minibatch (0.04 to 0.14 of it
 measured at 512 rows) and not for a single row, where it is not used.
 
+The six parameter gradients a minibatch ends with (check_grads) are sums over
+the rows of the stored tensors, so they are teacher-forced as well:
+
+  dW1 = dA1_k^T x, db1 = sum dA1_k;  dW2 = dA2_k^T h1_k, db2 = sum dA2_k;
+  dW3 = dz_k^T h2_k, db3 = sum dz_k  (where h2 and dz were stored; the fused
+  kernel's layer 3 stays with check_dw3)
+
+in fp64.  Nothing is rounded to bf16 on the way where the sum is an fp32 one
+(mas_policy_dw, the in-kernel dW3): FP32 (|a|^T |h|) + 1e-6 per element, the
+bound of test_policy_dw_matches_fp32.  The split-K GEMMs of masurvival.ppo
+(_splitk_nn for layer 1, _splitk_nt, _splitk_tn) are torch.bmm on bf16
+operands: each K-chunk's partial product S_c is rounded to bf16 before the
+fp32 sum over the chunks, half a bf16 ulp of each, so such a gradient carries
+BF16_HALF_ULP sum_c |S_c| on top, S_c the fp64 partial products of the chunks
+ppo._split_k(M) makes; their bias columns (the product with the ones column)
+the same with S_c = the chunk's column sums.  That term is the larger one by
+far: a GEMM gradient is 10 to 65 times the fp32 bound off (check_grads reports
+the figure as '<tensor>_x_fp32').
+
 Tensors here are row-major in natural feature order: h1, h2, dA1, dA2
 [M, 256], dz [M, 16]; the tests transpose / un-permute what the kernels store.
 """
@@ -113,14 +132,17 @@ def log_prob(z, acts):
     return lp
 
 
-def loss_rows(z, acts, old_logp, adv, ret, clip, vf_coef, ent_coef, scale):
+def loss_rows(z, acts, old_logp, adv, ret, clip, vf_coef, ent_coef, scale, row_w=None):
     """The per-row PPO loss and its gradient at z [M, 16] fp64, stated head by
     head from the formula of include/masurvival.h (no autograd):
       row i, head hd, output k:  scale (g_i (1[k = a_hd] - p_k) + ent_coef p_k (log p_k + H_hd)),
       g_i = -ratio adv where ratio adv <= clip(ratio) adv, else 0;
-      value: scale vf_coef 2 (v - ret)."""
+      value: scale vf_coef 2 (v - ret).
+    row_w [M] (mas_policy_train_w): row i's g_i and entropy term times w_i, the
+    value term as it is; 'w' of the result is that weight (ones without)."""
     dt = torch.float64
     z, old_logp, adv, ret = z.to(dt), old_logp.to(dt), adv.to(dt), ret.to(dt)
+    w = torch.ones_like(adv) if row_w is None else row_w.to(dt)
     lsms = head_log_softmax(z)
     lp = log_prob(z, acts)
     ratio = torch.exp(lp - old_logp)
@@ -134,10 +156,10 @@ def loss_rows(z, acts, old_logp, adv, ret, clip, vf_coef, ent_coef, scale):
         H = -(p * lsm).sum(1)
         ent = ent + H
         onehot = (torch.arange(n, device=z.device)[None, :] == acts[:, hd:hd + 1].long()).to(dt)
-        dz[:, off:off + n] = scale * (g[:, None] * (onehot - p) + ent_coef * p * (lsm + H[:, None]))
+        dz[:, off:off + n] = scale * w[:, None] * (g[:, None] * (onehot - p) + ent_coef * p * (lsm + H[:, None]))
     dv = z[:, 15] - ret
     dz[:, 15] = scale * vf_coef * 2.0 * dv
-    return dict(dz=dz, ratio=ratio, s1=s1, pg=-torch.minimum(s1, s2), vl=dv * dv, ent=ent,
+    return dict(dz=dz, ratio=ratio, s1=s1, pg=-torch.minimum(s1, s2), vl=dv * dv, ent=ent, w=w,
                 clipped=((ratio - 1.0).abs() > clip).to(dt))
 
 
@@ -151,7 +173,8 @@ def _logit_err(P, h2, c):
 
 def _dz_bound(L, d, cf):
     clip, vf, ec, sc = cf
-    return BF16_HALF_ULP * L['dz'].abs() + sc * d[:, None] * (8.0 * L['s1'].abs()[:, None] + 4.0 * ec + 2.0 * vf)
+    pol = L['w'][:, None] * (8.0 * L['s1'].abs()[:, None] + 4.0 * ec)  # the weighted terms (w = 1 without row_w)
+    return BF16_HALF_ULP * L['dz'].abs() + sc * d[:, None] * (pol + 2.0 * vf)
 
 
 def _worst(d, bound):
@@ -199,21 +222,104 @@ def check_rows(P, x, batch, cf, out, c=FP32):
     return res
 
 
-def check_dw3(P, x, batch, cf, gw, gb, c=FP32):
+def check_dw3(P, x, batch, cf, gw, gb, c=FP32, row_w=None, h2k=None):
     """Worst |d| / bound of the layer-3 gradients gw [16, 256], gb [16] against
     dz^T h2 and the column sums of dz of the unforced fp64 chain; the bound is
     the per-row bounds of check_rows summed over the rows (module docstring).
-    Returns {'dw3': .., 'db3': ..}."""
+    row_w: the rows' weights of mas_policy_train_dw3_w (loss_rows).
+    Returns {'dw3': .., 'db3': ..}.
+
+    h2k: the h2 [M, 256] a train kernel stored for these rows and this packed
+    policy (the unfused kernel's, whose data path is the fused one's): the
+    check is then teacher-forced on it, as check_rows is -- logits h2k W3^T +
+    b3, no h2 term in the bound.  That is what rows of a real rollout need:
+    the surrogate's gradient jumps at a clip boundary, and the bf16 rounding of
+    h1 and h2 moves a log-ratio by about 1e-3, so among a rollout's rows some
+    fall on the other side of a boundary in the unforced chain than in the
+    kernel, each by its whole surrogate term, which no rounding bound covers
+    (make_batch keeps its rows 0.01 away instead).  Forced, the kernel's ratio
+    is within 12 d_i of the reference's (six heads, each log-prob within twice
+    the logit error d_i); a row whose reference ratio is that close to the
+    boundary that counts for its advantage's sign may still fall on either
+    side, and the bound grants exactly those rows ('flip_rows' of the result)
+    their surrogate term."""
     acts, old_logp, adv, ret = batch
     clip, vf, ec, sc = cf
-    h1, h2, z = forward(P, x)
-    L = loss_rows(z, acts, old_logp, adv, ret, clip, vf, ec, sc)
+    if h2k is None:
+        h1, h2, z = forward(P, x)
+    else:
+        h2 = h2k.double()
+        z = h2 @ P['W3'].T + P['b3']
+    L = loss_rows(z, acts, old_logp, adv, ret, clip, vf, ec, sc, row_w)
     dz = L['dz']
-    bdz = _dz_bound(L, _logit_err(P, h2, c), cf)
-    bh2 = _tanh_bound(h2, h1.abs() @ P['W2'].abs().T + P['b2'].abs(), c)
-    bw = bdz.T @ h2.abs() + dz.abs().T @ bh2 + c * (dz.abs().T @ h2.abs()) + 1e-6
+    d = _logit_err(P, h2, c)
+    bdz = _dz_bound(L, d, cf)
+    res = {}
+    if h2k is None:
+        bh2 = _tanh_bound(h2, h1.abs() @ P['W2'].abs().T + P['b2'].abs(), c)
+        bw = bdz.T @ h2.abs() + dz.abs().T @ bh2 + c * (dz.abs().T @ h2.abs()) + 1e-6
+    else:
+        a = adv.double()
+        # s1 <= s2: ratio <= 1 + clip (adv > 0), ratio >= 1 - clip (adv < 0)
+        edge = torch.where(a > 0, 1.0 + clip, 1.0 - clip)
+        flip = (a != 0) & ((L['ratio'] - edge).abs() <= 12.0 * d * L['ratio'])
+        on = loss_rows(z, acts, old_logp, adv, ret, 1e30, vf, ec, sc, row_w)['dz']                     # never clipped
+        off = loss_rows(z, acts, old_logp, torch.zeros_like(adv), ret, clip, vf, ec, sc, row_w)['dz']  # no surrogate
+        bdz = bdz + flip[:, None] * (on - off).abs()
+        bw = bdz.T @ h2.abs() + c * (dz.abs().T @ h2.abs()) + 1e-6
+        res['flip_rows'] = int(flip.sum())
     bb = bdz.sum(0) + c * dz.abs().sum(0) + 1e-6
-    return {'dw3': _worst(gw.double() - dz.T @ h2, bw), 'db3': _worst(gb.double() - dz.sum(0), bb)}
+    res.update(dw3=_worst(gw.double() - dz.T @ h2, bw), db3=_worst(gb.double() - dz.sum(0), bb))
+    return res
+
+
+GRADS = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+
+
+def _check_layer(a, h, gw, gb, gemm, chunks, c):
+    """Worst |d| / bound of gw [F, G] against a^T h and of gb [F] against the
+    column sums of a (a [M, F], h [M, G], fp64); gemm: the bound carries the
+    bf16 rounding of the `chunks` partial products.  Returns (w, b, w over the
+    fp32-only bound, b over it)."""
+    M = a.shape[0]
+    dw, db = gw.double() - a.T @ h, gb.double() - a.sum(0)
+    bw = c * (a.abs().T @ h.abs()) + 1e-6
+    bb = c * a.abs().sum(0) + 1e-6
+    xw, xb = _worst(dw, bw), _worst(db, bb)
+    if not gemm:
+        return xw, xb, xw, xb
+    assert M % chunks == 0, (M, chunks)
+    ac, hc = a.reshape(chunks, M // chunks, -1), h.reshape(chunks, M // chunks, -1)
+    bw = bw + BF16_HALF_ULP * torch.bmm(ac.transpose(1, 2), hc).abs().sum(0)
+    bb = bb + BF16_HALF_ULP * ac.sum(1).abs().sum(0)
+    return _worst(dw, bw), _worst(db, bb), xw, xb
+
+
+def check_grads(x, out, grads, gemm=(1,), chunks=1, c=FP32):
+    """Worst |d| / bound of the parameter gradients `grads` (dict w1 [256, D],
+    b1, w2 [256, 256], b2 [256], w3 [16, 256], b3 [16]) against the fp64 sums
+    over the rows of the kernel's own stored tensors: x [M, D + 1] with the ones
+    column, and `out` with h1, da1, da2 and, where they were stored, h2 and dz
+    [M, F] in natural order (without them layer 3 is left out).  gemm: the
+    layers (1, 2, 3) whose gradient went through a bf16-output split-K GEMM of
+    `chunks` = ppo._split_k(M) chunks; the others are fp32 sums (module
+    docstring).  Returns {tensor: worst ratio} and, for the GEMM layers,
+    '<tensor>_x_fp32': the same error over the fp32-only bound."""
+    d = lambda t: t.double()  # noqa: E731
+    x = d(x)
+    D = x.shape[1] - 1
+    assert bool((x[:, D] == 1.0).all()), 'x: column D must be the ones column'
+    layers = [(1, d(out['da1']), x[:, :D]), (2, d(out['da2']), d(out['h1']))]
+    if 'h2' in out and 'dz' in out:
+        layers.append((3, d(out['dz']), d(out['h2'])))
+    res = {}
+    for n, a, h in layers:
+        wk, bk = f'w{n}', f'b{n}'
+        assert grads[wk].shape == (a.shape[1], h.shape[1]) and grads[bk].shape == (a.shape[1],), (wk, grads[wk].shape)
+        res[wk], res[bk], xw, xb = _check_layer(a, h, grads[wk], grads[bk], n in gemm, chunks, c)
+        if n in gemm:
+            res[wk + '_x_fp32'], res[bk + '_x_fp32'] = xw, xb
+    return res
 
 
 def make_batch(P, x, cf, gen, h2=None, zero_adv_every=5):
@@ -363,3 +469,71 @@ def emulate(P, x, batch, cf, mut=None):
     out['dw3'] = dz.T @ h2
     out['db3'] = dz.sum(0)
     return out
+
+
+# ---------------------------------------------------------------------------
+# The gradient assembly of FusedPolicy.grads on the host, from the stored
+# tensors of emulate(): fp32 sums (mas_policy_dw, the in-kernel dW3: any row
+# order) or the bf16-output split-K GEMMs of masurvival.ppo, with the named
+# assembly errors the checker's test requires check_grads to reject.
+
+# name -> the tensors that must reject it
+GRAD_MUTATIONS = {
+    'last_row_dropped': GRADS, 'row_counted_twice': GRADS,
+    'db_from_neighbour': ('b1', 'b2'), 'dw2_transposed': ('w2',), 'dw2_from_h2': ('w2',),
+    'dw1_bias_from_column_D-1': ('b1',), 'scale_1_over_M_missing': GRADS,
+    'rm_permutation_not_undone': ('w1', 'b1', 'w2', 'b2', 'w3'),
+}
+
+
+def stand_in_permutation():
+    """A feature -> stored column permutation of the 256 hidden features that
+    stays inside the 32-feature tiles, as the row-major kernel's does
+    (mas_policy_rm_feature; the host test has no library to ask)."""
+    g = torch.Generator().manual_seed(32)
+    return torch.cat([32 * t + torch.randperm(32, generator=g) for t in range(8)])
+
+
+def emulate_grads(x, out, mode='fp32', mut=None, gen=None):
+    """{w1 .. b3} from x [M, D + 1] (ones column included) and emulate()'s out.
+    mode 'fp32': fp32 matmuls over the rows in a shuffled order (gen);
+    'gemm': layer 1 through ppo._splitk_nn, layers 2 and 3 through
+    ppo._splitk_nt, on bf16 operands with the ones row, as FusedPolicy.grads
+    has them where mas_policy_dw does not apply."""
+    from masurvival import ppo
+    M, D = x.shape[0], x.shape[1] - 1
+    rows = torch.randperm(M, generator=gen) if mode == 'fp32' else torch.arange(M)
+    if mut == 'last_row_dropped':
+        rows = rows[rows != M - 1]
+    if mut == 'row_counted_twice':
+        rows = torch.cat([rows, torch.tensor([1 % M])])
+    T = {k: out[k].float()[rows] for k in ('h1', 'h2', 'da1', 'da2', 'dz')}
+    T['h2w'] = T['h2']
+    if mut == 'rm_permutation_not_undone':  # the stored column order kept where a feature index is meant
+        q = stand_in_permutation()
+        inv = torch.empty_like(q)
+        inv[q] = torch.arange(256)
+        T = {k: (v if k == 'dz' else v[:, inv]) for k, v in T.items()}
+    x = x.float()[rows]
+    ones = torch.ones((x.shape[0], 1))
+    pairs = {1: (T['da1'], x), 2: (T['da2'], torch.cat([T['h2' if mut == 'dw2_from_h2' else 'h1'], ones], 1)),
+             3: (T['dz'], torch.cat([T['h2w'], ones], 1))}
+    g = {}
+    for n, (a, h) in pairs.items():
+        if mode == 'fp32':
+            full = a.T @ h
+        elif n == 1:
+            full = ppo._splitk_nn(a.T.bfloat16(), h.bfloat16())
+        else:
+            full = ppo._splitk_nt(a.T.bfloat16(), h.T.bfloat16())
+        G = h.shape[1] - 1
+        g[f'w{n}'], g[f'b{n}'] = full[:, :G].clone(), full[:, G].clone()
+        if n == 1 and mut == 'dw1_bias_from_column_D-1':
+            g['b1'] = full[:, D - 1].clone()
+    if mut == 'dw2_transposed':
+        g['w2'] = g['w2'].T.clone()
+    if mut == 'db_from_neighbour':
+        g['b1'], g['b2'] = g['b2'], g['b1']
+    if mut == 'scale_1_over_M_missing':
+        g = {k: v * M for k, v in g.items()}
+    return g

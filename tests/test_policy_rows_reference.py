@@ -102,3 +102,100 @@ def test_layer3_gradient_bound_rejects_entropy_mutations(cset, mut):
     res = _run(160, 512, 'plain', cset, mut)
     print(cset, mut, round(res['dw3'], 1), round(res['db3'], 1))
     assert max(res['dw3'], res['db3']) >= REJECT, (mut, res)
+
+
+# --- the parameter gradients (policy_rows_ref.check_grads) ------------------
+
+GRAD_SHAPES = [(160, 326), (138, 77), (160, 8192)]  # the last: ppo._split_k makes two chunks
+
+
+@functools.lru_cache(maxsize=None)
+def _grad_case(D, M):
+    """(x with the ones column, the emulation's stored tensors, the chunk count)."""
+    from masurvival.ppo import _split_k
+    P, x, batch, cf = _case(D, M, 'plain', 'A')
+    x1 = torch.cat([x.float(), torch.ones((M, 1))], 1)
+    return x1, R.emulate(P, x, batch, cf), _split_k(M)
+
+
+@functools.lru_cache(maxsize=None)
+def _grads(D, M, mode, mut=None):
+    x1, out, _ = _grad_case(D, M)
+    return R.emulate_grads(x1, out, mode, mut, torch.Generator().manual_seed(M))
+
+
+def test_split_k_chunks_of_the_gradient_shapes():
+    assert [_grad_case(D, M)[2] for D, M in GRAD_SHAPES] == [1, 1, 2]
+
+
+@pytest.mark.parametrize('D,M', GRAD_SHAPES)
+def test_gradient_emulation_passes_the_checker(D, M):
+    x1, out, chunks = _grad_case(D, M)
+    fp32 = R.check_grads(x1, out, _grads(D, M, 'fp32'), gemm=(), chunks=chunks)
+    gemm = R.check_grads(x1, out, _grads(D, M, 'gemm'), gemm=(1, 2, 3), chunks=chunks)
+    print(D, M, 'fp32', {k: round(v, 3) for k, v in fp32.items()})
+    print(D, M, 'gemm', {k: round(v, 3) for k, v in gemm.items()})
+    for k in R.GRADS:
+        assert fp32[k] <= 1.0, (k, fp32)
+        assert gemm[k] <= 1.0, (k, gemm)
+    # the layers mixed as FusedPolicy.grads mixes them: layer 1 a GEMM, 2 and 3 fp32 sums
+    mixed = dict(_grads(D, M, 'fp32'), w1=_grads(D, M, 'gemm')['w1'], b1=_grads(D, M, 'gemm')['b1'])
+    res = R.check_grads(x1, out, mixed, gemm=(1,), chunks=chunks)
+    for k in R.GRADS:
+        assert res[k] <= 1.0, (k, res)
+    # without h2 and dz (the fused kernel stores neither) layer 3 is left out
+    res = R.check_grads(x1, {k: out[k] for k in ('h1', 'da1', 'da2')}, mixed, gemm=(1,), chunks=chunks)
+    assert sorted(k for k in res if k in R.GRADS) == ['b1', 'b2', 'w1', 'w2']
+
+
+@pytest.mark.parametrize('mut', sorted(R.GRAD_MUTATIONS))
+@pytest.mark.parametrize('mode', ['fp32', 'gemm'])
+@pytest.mark.parametrize('D,M', [(160, 326), (138, 77)])
+def test_gradient_checker_rejects_mutation(D, M, mode, mut):
+    x1, out, chunks = _grad_case(D, M)
+    res = R.check_grads(x1, out, _grads(D, M, mode, mut), gemm=(1, 2, 3) if mode == 'gemm' else (), chunks=chunks)
+    print(D, M, mode, mut, {k: round(res[k], 2) for k in R.GRADS})
+    for k in R.GRAD_MUTATIONS[mut]:
+        assert res[k] > 1.0, (mut, k, res)
+
+
+@pytest.mark.parametrize('D,M', GRAD_SHAPES)
+def test_gemm_layer1_gradient_exceeds_the_fp32_bound(D, M):
+    """dW1 through the bf16-output GEMM, declared an fp32 sum: rejected.  The
+    rounding of the chunk products to bf16 is many times the fp32 bound (the
+    figure printed; 65x / 20x / 11x on random operands at M = 512 / 8192 /
+    16384), which is why check_grads carries BF16_HALF_ULP sum |S_c| for it."""
+    x1, out, chunks = _grad_case(D, M)
+    g = _grads(D, M, 'gemm')
+    res = R.check_grads(x1, out, g, gemm=(), chunks=chunks)
+    ok = R.check_grads(x1, out, g, gemm=(1, 2, 3), chunks=chunks)
+    print(D, M, 'w1 over the fp32-only bound', round(res['w1'], 1), 'over the GEMM bound', round(ok['w1'], 3))
+    assert res['w1'] > 1.0, res
+    assert ok['w1_x_fp32'] == res['w1'] and ok['w1'] <= 1.0
+
+
+def test_layer3_gradient_check_forced_on_the_stored_h2():
+    """check_dw3 teacher-forced on the emulation's stored h2 (h2k): the clean
+    sums pass, no row is granted a clip flip (make_batch keeps the ratios 0.01
+    from the boundaries), the bound is the tighter one, and an entropy error
+    is still rejected."""
+    P, x, batch, cf = _case(160, 512, 'plain', 'C')
+    out = R.emulate(P, x, batch, cf)
+    un = R.check_dw3(P, x, batch, cf, out['dw3'], out['db3'])
+    fo = R.check_dw3(P, x, batch, cf, out['dw3'], out['db3'], h2k=out['h2'])
+    print('unforced', un, 'forced', fo)
+    assert fo['flip_rows'] == 0 and fo['dw3'] <= 1.0 and fo['db3'] <= 1.0
+    bad = R.emulate(P, x, batch, cf, 'entropy_sign')
+    res = R.check_dw3(P, x, batch, cf, bad['dw3'], bad['db3'], h2k=bad['h2'])
+    assert max(res['dw3'], res['db3']) >= REJECT, res
+    # a row moved onto its clip boundary is granted its surrogate term, and only then
+    acts, old_logp, adv, ret = batch
+    z = out['h2'].double() @ P['W3'].T + P['b3']
+    i = int(torch.nonzero(adv > 0)[0])
+    lp2 = old_logp.clone()
+    lp2[i] = float(R.log_prob(z, acts)[i] - torch.log(torch.tensor(1.0 + cf[0], dtype=torch.float64)))
+    b2 = (acts, lp2, adv, ret)
+    o2 = R.emulate(P, x, b2, cf)
+    r2 = R.check_dw3(P, x, b2, cf, o2['dw3'], o2['db3'], h2k=o2['h2'])
+    print('one row on the boundary', r2)
+    assert r2['flip_rows'] == 1 and r2['dw3'] <= 1.0 and r2['db3'] <= 1.0
