@@ -56,6 +56,15 @@ MAS_DECLARE(xxl)
 hipError_t rows_select(int64_t n_envs, int n_agents, uint32_t mask, const void* x, int64_t x_stride, void* x_out,
                        int64_t x_out_stride, int x_cols, const int8_t* act, int8_t* act_out, int n_f32,
                        const float* const* f_in, float* const* f_out, hipStream_t s);
+// observation statistics, their running merge and the folded pack (mas_obsnorm.hip)
+int64_t obs_stats_scratch_doubles(int64_t n_rows, int n_cols);
+hipError_t obs_stats(int64_t n_rows, int n_cols, const void* x, int64_t x_stride, double* sums, double* scratch,
+                     hipStream_t s);
+hipError_t obs_norm_merge(int n_cols, double* state, const double* batch, double eps, float* mean_out,
+                          float* inv_std_out, hipStream_t s);
+hipError_t policy_pack_norm(int D, const float* W1, const float* b1, const float* W2, const float* b2,
+                            const float* W3, const float* b3, const float* mean, const float* inv_std, void* packed,
+                            hipStream_t s);
 }  // namespace mas
 
 namespace {
@@ -1286,6 +1295,58 @@ int mas_rows_select(int64_t n_envs, int32_t n_agents, uint32_t agent_mask, const
     if (n_envs == 0) return MAS_OK;
     HIP_TRY(rows_select(n_envs, n_agents, agent_mask, x_bf16, x_stride, x_out, x_out_stride, x_cols, actions,
                         actions_out, n_f32, f32_in, f32_out, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int64_t mas_obs_stats_scratch_doubles(int64_t n_rows, int32_t n_cols)
+{
+    return n_rows >= 0 && n_cols >= 1 ? obs_stats_scratch_doubles(n_rows, n_cols) : -1;
+}
+
+int mas_obs_stats(int64_t n_rows, int32_t n_cols, const void* x_bf16, int64_t x_stride, double* sums,
+                  double* scratch, void* stream)
+{
+    // every check before any HIP call
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (n_rows < 0) return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: n_rows must not be negative");
+    if (x_stride <= 0 || (x_stride % 8) != 0)
+        return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: x_stride must be a positive multiple of 8");
+    if (n_cols < 1 || n_cols > x_stride) return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: n_cols must be in 1..x_stride");
+    if (!sums || !scratch) return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: null sums or scratch");
+    if ((addr(sums) | addr(scratch)) & 7)
+        return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: sums and scratch must be 8-B aligned");
+    if (n_rows > 0 && !x_bf16) return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: null x_bf16");
+    if (addr(x_bf16) & 15) return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: x_bf16 must be 16-B aligned");
+    if (n_rows > (INT64_MAX >> 8) / x_stride)
+        return fail(MAS_ERR_INVALID_ARG, "mas_obs_stats: n_rows too large (byte offsets past 2^63)");
+    HIP_TRY(obs_stats(n_rows, n_cols, x_bf16, x_stride, sums, scratch, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int mas_obs_norm_merge(int32_t n_cols, double* state, const double* batch, double eps, float* mean_out,
+                       float* inv_std_out, void* stream)
+{
+    const auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (n_cols < 1) return fail(MAS_ERR_INVALID_ARG, "mas_obs_norm_merge: n_cols must be positive");
+    if (!state || !batch || !mean_out || !inv_std_out)
+        return fail(MAS_ERR_INVALID_ARG, "mas_obs_norm_merge: null state, batch, mean_out or inv_std_out");
+    if (((addr(state) | addr(batch)) & 7) || ((addr(mean_out) | addr(inv_std_out)) & 3))
+        return fail(MAS_ERR_INVALID_ARG, "mas_obs_norm_merge: misaligned array (state, batch 8 B; outputs 4 B)");
+    if (!(eps >= 0.0) || std::isinf(eps))
+        return fail(MAS_ERR_INVALID_ARG, "mas_obs_norm_merge: eps must be finite and not negative");
+    HIP_TRY(obs_norm_merge(n_cols, state, batch, eps, mean_out, inv_std_out, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int mas_policy_pack_norm(int32_t obs_dim, const float* w1, const float* b1, const float* w2, const float* b2,
+                         const float* w3, const float* b3, const float* mean, const float* inv_std, void* packed,
+                         void* stream)
+{
+    if (obs_dim <= 0 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !packed)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_pack_norm: bad argument");
+    if (!mean != !inv_std)
+        return fail(MAS_ERR_INVALID_ARG, "mas_policy_pack_norm: mean and inv_std must both be given or both be null");
+    HIP_TRY(policy_pack_norm(obs_dim, w1, b1, w2, b2, w3, b3, mean, inv_std, packed, (hipStream_t)stream));
     return MAS_OK;
 }
 

@@ -95,6 +95,10 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     'mas_rows_select': (c_int32, [c_int64, c_int32, ctypes.c_uint32, c_void_p, c_int64, c_void_p, c_int64, c_int32,
                                   c_void_p, c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    'mas_obs_stats_scratch_doubles': (c_int64, [c_int64, c_int32]),
+    'mas_obs_stats': (c_int32, [c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'mas_obs_norm_merge': (c_int32, [c_int32, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    'mas_policy_pack_norm': (c_int32, [c_int32] + [c_void_p] * 10),
     'mas_policy_train': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p] * 7),
     'mas_policy_train_ld': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
     'mas_policy_train_dw3': (c_int32, _TRAIN_HEAD + _TRAIN_COEFS + [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
@@ -116,7 +120,8 @@ SIGNATURES = {
 # additions within ABI version 3 that an older build of the library (an A/B
 # variant loaded through MAS_LIB) may lack; their callers test with hasattr
 OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel', 'mas_rows_select', 'mas_alive', 'mas_policy_train_w',
-            'mas_policy_train_dw3_w'}
+            'mas_policy_train_dw3_w', 'mas_obs_stats_scratch_doubles', 'mas_obs_stats', 'mas_obs_norm_merge',
+            'mas_policy_pack_norm'}
 
 MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 

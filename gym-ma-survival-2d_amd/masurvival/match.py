@@ -19,7 +19,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .ppo import HEADS, FusedPolicy, PolicyMLP, sample_actions
+from .ppo import HEADS, FusedPolicy, ObsNorm, PolicyMLP, sample_actions
 
 _COUNT_EVERY = 32  # run(episodes=...) reads the device's episode count every this many steps
 
@@ -27,13 +27,18 @@ _COUNT_EVERY = 32  # run(episodes=...) reads the device's episode count every th
 def load_policy(src, device='cpu') -> PolicyMLP:
     """The PolicyMLP of a checkpoint: `src` is a path (read with
     ``weights_only=True``) or an already loaded dict; only ``src['policy']`` is
-    read, and obs_dim comes from ``body.0.weight``."""
+    read, and obs_dim comes from ``body.0.weight``.  A checkpoint with an
+    ``'obs_norm'`` entry (``PPOConfig.obs_norm``) gives a policy with that
+    normaliser attached: it acts on raw observations as the trainer's did."""
     if isinstance(src, (str, bytes, os.PathLike)):
         src = torch.load(src, map_location='cpu', weights_only=True)
     sd = src['policy']
     hidden, obs_dim = sd['body.0.weight'].shape
     policy = PolicyMLP(int(obs_dim), int(hidden))
     policy.load_state_dict(sd)
+    if 'obs_norm' in src:
+        on = ObsNorm.from_state_dict(src['obs_norm'], 'cpu')
+        policy.set_obs_norm(on.mean, on.inv_std)
     return policy.to(device).eval()
 
 

@@ -37,6 +37,17 @@ the next, possibly dead, row.  Multi-GPU: every rank normalises its minibatch by
 its own active count and the ranks' gradients are averaged as before, so a rank
 with few active rows weighs each of them more than a global normalisation
 would -- an approximation that costs no extra collective.
+
+Observation normalisation (``PPOConfig.obs_norm``): a running per-column mean
+and variance of the policy's bf16 input rows (``ObsNorm``: ``mas_obs_stats``
+over the rollout's rows, Chan's merge in fp64), folded into the packed layer-1
+weights (``mas_policy_pack_norm``) instead of applied to a row: the act and
+train kernels and the rollout buffer keep raw rows.  The constructor merges the
+reset rows, ``iteration()`` merges the rows it has just trained on and packs
+again, so rollout k and update k see one normaliser (the reset rows are
+counted twice, once in a lifetime: as block 0 of the first rollout too).
+Nothing clips a normalised value: ``obs_norm_eps`` (the variance floor) is the
+only bound, ``inv_std <= 1 / sqrt(eps)`` (10 by default).
 """
 from __future__ import annotations
 
@@ -104,6 +115,14 @@ class PPOConfig:
     # weight the policy terms of the loss (surrogate, entropy) by the agents'
     # alive flags (env.alive()), see the module docstring; off: every row alike
     mask_dead: bool = False
+    # running per-column mean / variance normalisation of the observations,
+    # folded into the packed layer-1 weights (module docstring); off: the same
+    # launches and bits as without it
+    obs_norm: bool = False
+    # the variance floor: inv_std = 1 / sqrt(var + eps) <= 1 / sqrt(eps).  The
+    # fold cannot clip a normalised value (VecNormalize clips at +-10), so
+    # this alone bounds how far a near-constant column is amplified
+    obs_norm_eps: float = 1e-2
 
 
 def _split_k(m: int, cap: int = int(os.environ.get('MAS_SPLITK_CAP', '128'))) -> int:
@@ -153,14 +172,37 @@ class PolicyMLP(nn.Module):
         super().__init__()
         self.body = nn.Sequential(LinearSplitK(obs_dim, hidden), nn.Tanh(), LinearSplitK(hidden, hidden), nn.Tanh())
         self.head = LinearSplitK(hidden, N_LOGITS + 1)
+        # the optional input normaliser (set_obs_norm): non-persistent buffers,
+        # so state_dict() keeps its keys and old checkpoints load, while
+        # deepcopy and .to() carry them along
+        self.register_buffer('obs_mean', None, persistent=False)
+        self.register_buffer('obs_inv_std', None, persistent=False)
+
+    def set_obs_norm(self, mean, inv_std):
+        """Attach (mean, inv_std) [obs_dim] -- the tensors themselves, so an
+        ObsNorm that updates them in place updates this policy -- or detach
+        with (None, None): forward then computes on (x - mean) * inv_std."""
+        if (mean is None) != (inv_std is None):
+            raise ValueError('set_obs_norm: mean and inv_std go together')
+        if mean is not None:
+            d = self.body[0].weight.shape[1]
+            if mean.shape != (d,) or inv_std.shape != (d,):
+                raise ValueError(f'set_obs_norm: expected two [{d}] tensors, got {tuple(mean.shape)} and '
+                                 f'{tuple(inv_std.shape)}')
+        self.obs_mean, self.obs_inv_std = mean, inv_std
+
+    def _normed(self, x):
+        if self.obs_mean is None:
+            return x
+        return (x - self.obs_mean) * self.obs_inv_std
 
     def forward(self, x):
-        h = self.head(self.body(x))
+        h = self.head(self.body(self._normed(x)))
         return h[..., :N_LOGITS].float(), h[..., N_LOGITS].float()
 
     def forward_raw(self, x):
         """[.., 16] fp32 head output: 15 logits then the value."""
-        return self.head(self.body(x)).float()
+        return self.head(self.body(self._normed(x))).float()
 
 
 def _split_heads(logits):
@@ -325,6 +367,144 @@ def rows_select(n_agents, agent_mask, x=None, x_out=None, x_cols=None, actions=N
                               ptr(actions), ptr(actions_out), n, fin, fout, ctypes.c_void_p(st)))
 
 
+def obs_moments_reference(x_rows, n_cols):
+    """Plain torch restatement of mas_obs_stats: fp64 [2, n_cols], the sums
+    and the sums of squares of columns [0, n_cols) over all rows of x_rows
+    [.., >= n_cols] (bf16 rows, or anything exactly representable in fp64)."""
+    x = x_rows.reshape(-1, x_rows.shape[-1])[:, :n_cols].to(torch.float64)
+    return torch.stack([x.sum(0), (x * x).sum(0)])
+
+
+def merge_reference(state, batch, eps):
+    """Plain torch fp64 restatement of mas_obs_norm_merge: state
+    [1 + 2 n_cols] = (count, mean, m2) is updated in place from batch
+    [1 + 2 n_cols] = (count_b, sums, sums of squares); returns the fp32
+    (mean, inv_std), the identity (0, 1) while the count is 0."""
+    n_cols = (state.numel() - 1) // 2
+    count, nb = state[0].clone(), batch[0]
+    mean, m2 = state[1:1 + n_cols], state[1 + n_cols:]
+    n = count + nb
+    if float(nb) > 0:
+        mean_b = batch[1:1 + n_cols] / nb
+        m2_b = (batch[1 + n_cols:] - nb * mean_b * mean_b).clamp_min(0.0)
+        d = mean_b - mean
+        mean += d * nb / n
+        m2 += m2_b + d * d * count * nb / n
+        state[0] = n
+    if float(n) > 0:
+        return mean.float(), (1.0 / torch.sqrt(m2 / n + eps)).float()
+    return torch.zeros_like(mean, dtype=torch.float32), torch.ones_like(mean, dtype=torch.float32)
+
+
+def unfold_dw1(g1w, g1b, mean, inv_std):
+    """dL/dW1 of the normalised form h = W1 ((x - mean) * inv_std) + b1 from
+    the gradient (g1w [F, D], g1b [F]) of the folded form h = W1' x + b1' the
+    kernels compute on raw rows (W1' = W1 diag(inv_std), b1' = b1 - W1' mean):
+    dW1 = (g1w - g1b (x) mean) * inv_std.  db1 is g1b itself."""
+    return (g1w - g1b.unsqueeze(1) * mean) * inv_std
+
+
+class ObsNorm:
+    """Running per-column mean / variance of the policy's input rows: the fp64
+    state (count, mean[], m2[]) and the fp32 ``mean`` / ``inv_std`` made from
+    it (inv_std = 1 / sqrt(m2 / count + eps); 0 and 1 while the count is 0),
+    all on `device`.  On a GPU ``update`` is mas_obs_stats + mas_obs_norm_merge
+    (include/masurvival.h); ``update_reference`` and the CPU are the torch
+    restatement (obs_moments_reference, merge_reference).  ``mean`` and
+    ``inv_std`` are updated in place: a PolicyMLP they are attached to
+    (set_obs_norm) follows."""
+
+    def __init__(self, n_cols, device, eps=1e-2):
+        self.n_cols, self.device, self.eps = int(n_cols), torch.device(device), float(eps)
+        self.state = torch.zeros((1 + 2 * self.n_cols,), dtype=torch.float64, device=self.device)
+        self.batch = torch.zeros_like(self.state)
+        self.mean = torch.zeros((self.n_cols,), dtype=torch.float32, device=self.device)
+        self.inv_std = torch.ones((self.n_cols,), dtype=torch.float32, device=self.device)
+        self._scratch = None
+        self.lib = None
+        if self.device.type == 'cuda':
+            self.lib = load_library()
+            if not hasattr(self.lib, 'mas_obs_stats'):
+                raise MasError('the loaded library has no mas_obs_stats')
+
+    @property
+    def count(self):
+        return self.state[0]
+
+    def _merge(self, group, reduce):
+        if reduce:
+            dist.all_reduce(self.batch, group=group)
+        if self.lib is not None:
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+            check(self.lib.mas_obs_norm_merge(self.n_cols, ptr(self.state), ptr(self.batch), self.eps, ptr(self.mean),
+                                              ptr(self.inv_std),
+                                              ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        else:
+            mean, inv_std = merge_reference(self.state, self.batch, self.eps)
+            self.mean.copy_(mean)
+            self.inv_std.copy_(inv_std)
+
+    @torch.no_grad()
+    def update(self, x_rows_bf16, group=None, reduce=None):
+        """Merge the bf16 rows x_rows_bf16 [rows, stride] (unit column stride,
+        a row stride that is a multiple of 8; columns [0, n_cols) count) into
+        the state.  reduce (default: whether a group is given): all-reduce the
+        batch record (count, sums, sums of squares) over `group` first, so
+        every rank ends with the same state."""
+        x = x_rows_bf16
+        if x.dtype != torch.bfloat16 or x.dim() != 2 or x.shape[1] < self.n_cols or x.device.type != self.device.type:
+            raise ValueError(f'ObsNorm.update: need bf16 [rows, >= {self.n_cols}] rows on {self.device}')
+        if self.lib is None:
+            return self.update_reference(x, group, reduce)
+        self.batch[:1].fill_(float(x.shape[0]))  # (the all-reduce sums the ranks' counts in place)
+        if x.stride(1) != 1 or x.stride(0) % 8 != 0:
+            raise ValueError('ObsNorm.update: rows need unit column stride and a row stride that is a multiple of 8')
+        need = int(self.lib.mas_obs_stats_scratch_doubles(x.shape[0], self.n_cols))
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty((max(need, 1),), dtype=torch.float64, device=self.device)
+        check(self.lib.mas_obs_stats(x.shape[0], self.n_cols, ctypes.c_void_p(x.data_ptr()), x.stride(0),
+                                     ctypes.c_void_p(self.batch.data_ptr() + 8),
+                                     ctypes.c_void_p(self._scratch.data_ptr()),
+                                     ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._merge(group, group is not None if reduce is None else reduce)
+
+    @torch.no_grad()
+    def update_reference(self, x_rows, group=None, reduce=None):
+        """update() with the moments from the torch restatement: for rows that
+        are not the kernels' (any row stride, any device)."""
+        self.batch[:1].fill_(float(x_rows.reshape(-1, x_rows.shape[-1]).shape[0]))
+        self.batch[1:].copy_(obs_moments_reference(x_rows, self.n_cols).reshape(-1))
+        self._merge(group, group is not None if reduce is None else reduce)
+
+    @torch.no_grad()
+    def refresh(self):
+        """mean / inv_std again from the state (a merge of an empty batch)."""
+        self.batch.zero_()
+        self._merge(None, False)
+
+    def state_dict(self):
+        n = self.n_cols
+        return {'count': self.state[0].detach().clone(), 'mean': self.state[1:1 + n].detach().clone(),
+                'm2': self.state[1 + n:].detach().clone(), 'eps': float(self.eps)}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        n = self.n_cols
+        if sd['mean'].shape != (n,) or sd['m2'].shape != (n,):
+            raise ValueError(f'ObsNorm: checkpoint statistics of {tuple(sd["mean"].shape)} columns, expected {n}')
+        self.state[0] = sd['count'].to(torch.float64)
+        self.state[1:1 + n].copy_(sd['mean'])
+        self.state[1 + n:].copy_(sd['m2'])
+        self.eps = float(sd.get('eps', self.eps))
+        self.refresh()
+
+    @classmethod
+    def from_state_dict(cls, sd, device):
+        on = cls(sd['mean'].numel(), device, sd.get('eps', 1e-2))
+        on.load_state_dict(sd)
+        return on
+
+
 def gae_reference(rewards, values, dones, gamma, lam, n_agents):
     """Plain torch fp32 restatement of mas_gae (the numerics test's reference)."""
     T = rewards.shape[0]
@@ -436,6 +616,14 @@ class FusedPolicy:
         p = self.policy
         ts = [p.body[0].weight, p.body[0].bias, p.body[2].weight, p.body[2].bias, p.head.weight, p.head.bias]
         ts = [t.detach().float().contiguous() for t in ts]
+        if p.obs_mean is not None:
+            # the input normaliser folded into layer 1 (mas_policy_pack_norm)
+            if not hasattr(self.lib, 'mas_policy_pack_norm'):
+                raise MasError('the loaded library has no mas_policy_pack_norm')
+            ts += [p.obs_mean.detach().float().contiguous(), p.obs_inv_std.detach().float().contiguous()]
+            check(self.lib.mas_policy_pack_norm(self.D, *[ctypes.c_void_p(t.data_ptr()) for t in ts],
+                                                ctypes.c_void_p(self.packed.data_ptr()), self._stream()))
+            return
         check(self.lib.mas_policy_pack(self.D, *[ctypes.c_void_p(t.data_ptr()) for t in ts],
                                        ctypes.c_void_p(self.packed.data_ptr()), self._stream()))
 
@@ -534,6 +722,18 @@ class FusedPolicy:
             else:
                 prm.grad.copy_(g)
 
+    def _dw1(self, g1):
+        """Layer 1's weight gradient from g1 = dA1 [x, 1] over the raw rows
+        ([256, D + 1]): its first D columns, unfolded (unfold_dw1) when the
+        policy carries an input normaliser -- the kernels differentiated the
+        folded W1'.  In fp64, rounded once: g1w and g1b (x) mean nearly cancel in
+        a column that sits far from zero."""
+        p = self.policy
+        if p.obs_mean is None:
+            return g1[:, :self.D]
+        return unfold_dw1(g1[:, :self.D].double(), g1[:, self.D].double(), p.obs_mean.double(),
+                          p.obs_inv_std.double()).float()
+
     @staticmethod
     def _loss_stats(part, M, cfg):
         """(loss, pg, v, entropy, clipfrac) from the train kernel's partial records."""
@@ -551,11 +751,12 @@ class FusedPolicy:
         g2 = _splitk_tn(B['da2'], B['h1'][:, :257])              # [256, 257]
         g1 = _splitk_tn(B['da1'], xb[:, :self.D + 1])            # [256, D + 1]
         g2 = g2.index_select(0, q)
+        g1 = g1.index_select(0, q)
         p = self.policy
         l1, l2, l3 = p.body[0], p.body[2], p.head
         self._set_grads({l3.weight: g3[:, :256].index_select(1, q), l3.bias: g3[:, 256],
                          l2.weight: g2[:, :256].index_select(1, q), l2.bias: g2[:, 256],
-                         l1.weight: g1.index_select(0, q)[:, :self.D], l1.bias: g1[:, self.D].index_select(0, q)})
+                         l1.weight: self._dw1(g1), l1.bias: g1[:, self.D]})
         return self._loss_stats(B['part'], M, cfg)
 
     def _buffers(self, M):
@@ -683,7 +884,7 @@ class FusedPolicy:
         g1 = _splitk_nn(B['da1'], xb[:, :self.D + 1])  # [256, D + 1]
         # (a None gradient: written in place above)
         self._set_grads({l3.weight: g3w, l3.bias: g3b, l2.weight: g2w, l2.bias: g2b,
-                         l1.weight: g1[:, :self.D], l1.bias: g1[:, self.D]})
+                         l1.weight: self._dw1(g1), l1.bias: g1[:, self.D]})
         return self._loss_stats(B['part'], M, cfg) if stats else None
 
 
@@ -918,6 +1119,12 @@ class PPOTrainer:
         self.seed = int(seed) * 1000003 + (dist.get_rank() if dist.is_initialized() else 0)
         self.steps_taken = 0
         self._rollout_policy = None
+        # the input normaliser (ObsNorm), attached to the policy; also made by
+        # load_state_dict from a checkpoint that has one.  cfg.obs_norm only
+        # decides whether it keeps updating
+        self.obs_norm = None
+        if cfg.obs_norm:
+            self._attach_obs_norm(ObsNorm(env.obs_dim, self.device, cfg.obs_norm_eps))
         fused = cfg.fused
         if fused is None:
             fused = self.device.type == 'cuda' and cfg.hidden == 256
@@ -940,15 +1147,58 @@ class PPOTrainer:
             M = b.N * b.A
             self._boot = (torch.empty((M, 6), dtype=torch.int8, device=self.device),
                           torch.empty((M,), dtype=torch.float32, device=self.device))
+            if cfg.obs_norm:
+                self._obs_norm_merge_reset()  # the first rollout is already scaled
             self.fused.pack()
             if cfg.mask_dead and self.fused.layout == 'rm':
                 raise ValueError('PPOConfig.mask_dead needs the feature-major update (MAS_POL_LAYOUT=fm)')
             if _FUSED_ADAM and FusedAdam.supports(self.opt):
                 self.fused_opt = FusedAdam(self.policy.parameters(), self.opt, self.fused.lib, self.device)
         else:
+            if cfg.obs_norm:
+                self._obs_norm_merge_reset()
             self._sync_rollout_policy()
         if self.learner_agents is not None:
             self._init_selfplay()
+
+    def _attach_obs_norm(self, on):
+        self.obs_norm = on
+        self.policy.set_obs_norm(on.mean, on.inv_std)
+
+    @torch.no_grad()
+    def _obs_norm_merge_reset(self):
+        """Merge time block 0, the reset rows (with self-play the learner's),
+        before the first rollout; they count again as block 0 of that rollout."""
+        b = self.buf
+        if self.x_obs:
+            rows = b.xb[0].view(b.N, b.A, -1)
+        else:
+            rows = b.obs[0].to(torch.bfloat16)  # rounded as the kernels round
+        if self.learner_agents is not None:
+            rows = rows[:, self.learner_agents]
+        self._obs_norm_update(rows.reshape(-1, rows.shape[-1]), kernel=self.x_obs)
+
+    def _obs_norm_update(self, rows, kernel):
+        """rows bf16 [M, >= D] into the normaliser: mas_obs_stats where the
+        rows are the kernels' (kernel), else the torch restatement; the batch
+        record all-reduced first when this trainer runs collectives."""
+        if kernel:
+            self.obs_norm.update(rows.contiguous(), group=self.group, reduce=self.collectives)
+        else:
+            self.obs_norm.update_reference(rows, group=self.group, reduce=self.collectives)
+
+    @torch.no_grad()
+    def _obs_norm_after_update(self):
+        """Merge the rows the update has just trained on (blocks [0, T); with
+        self-play the learner's dense rows), before block 0 is overwritten; the
+        callers then pack / sync, so the next rollout and its update see the
+        new normaliser and a first minibatch's ratios stay 1."""
+        full, T = self.buf, self.cfg.horizon
+        b = full if full.learner is None else full.learner
+        if self.fused is not None:
+            self._obs_norm_update(b.xb[:T].view(-1, self.fused.Dx), kernel=True)
+        else:
+            self._obs_norm_update(b.obs[:T].reshape(-1, b.D).to(torch.bfloat16), kernel=False)
 
     @staticmethod
     def _resolve_selfplay(env, opponent, learner_agents):
@@ -1021,6 +1271,9 @@ class PPOTrainer:
             raise ValueError('sync_opponent: this trainer has no opponent')
         for d, s_ in zip(self.opponent.parameters(), self.policy.parameters()):
             d.copy_(s_)
+        # (a copy of the normaliser as it is now: the learner's keeps moving)
+        mean, inv_std = self.policy.obs_mean, self.policy.obs_inv_std
+        self.opponent.set_obs_norm(*((None, None) if mean is None else (mean.clone(), inv_std.clone())))
         if self.opp_fused is not None:
             self.opp_fused.pack()
 
@@ -1045,6 +1298,9 @@ class PPOTrainer:
                 self._rollout_policy = copy.deepcopy(self.policy).to(torch.bfloat16)
             for d, s_ in zip(self._rollout_policy.parameters(), self.policy.parameters()):
                 d.copy_(s_)
+            if self.policy.obs_mean is not None:
+                self._rollout_policy.set_obs_norm(self.policy.obs_mean.to(torch.bfloat16),
+                                                  self.policy.obs_inv_std.to(torch.bfloat16))
 
     @torch.no_grad()
     def _rollout_step_selfplay(self, t):
@@ -1235,6 +1491,9 @@ class PPOTrainer:
                            'clipfrac': cf.detach()}
         if share is not None:
             self.last_stats['active'] = share
+        if c.obs_norm:
+            self._obs_norm_after_update()
+            self.fused.pack()
         if self.x_obs:
             full.xb[0].copy_(full.xb[c.horizon])
         else:
@@ -1272,6 +1531,8 @@ class PPOTrainer:
         self.last_stats = {'loss': loss.detach(), 'pg': pg.detach(), 'v': vl.detach()}
         if share is not None:
             self.last_stats['active'] = share[0]
+        if c.obs_norm:
+            self._obs_norm_after_update()
         self._sync_rollout_policy()
         full.obs[0].copy_(full.obs[c.horizon])
 
@@ -1289,12 +1550,17 @@ class PPOTrainer:
               'gen': self.gen.get_state(), 'obs0': self.buf.obs[0].detach().clone()}
         if self.x_obs:
             sd['xb0'] = self.buf.xb[0].detach().clone()  # (x_obs: the next rollout's rows; obs0 is the reset's)
+        if self.obs_norm is not None:
+            sd['obs_norm'] = self.obs_norm.state_dict()  # three fp64 tensors and eps (match.load_policy reads it)
         if self.learner_agents is not None:
             # self-play: 'policy' stays the learner (match.load_policy reads it as any checkpoint's)
             sd['learner_agents'] = [int(a) for a in self.learner_agents]
             sd['iterations'] = int(self.iterations)
             if self.opponent is not None:
                 sd['opponent'] = {k: v.detach().clone() for k, v in self.opponent.state_dict().items()}
+                if self.opponent.obs_mean is not None:  # the frozen normaliser as the opponent applies it
+                    sd['opponent_obs_norm'] = {'mean': self.opponent.obs_mean.detach().clone(),
+                                               'inv_std': self.opponent.obs_inv_std.detach().clone()}
         if hasattr(self.env, 'get_state'):
             sd['env'] = self.env.get_state().detach().clone()
             if hasattr(self.env, 'state_meta'):
@@ -1313,10 +1579,18 @@ class PPOTrainer:
             raise ValueError('checkpoint and trainer disagree on having an opponent')
         if self.opponent is not None:
             self.opponent.load_state_dict(sd['opponent'])
+            on = sd.get('opponent_obs_norm')
+            self.opponent.set_obs_norm(*((None, None) if on is None else
+                                         (on['mean'].to(self.device).float(), on['inv_std'].to(self.device).float())))
             if self.opp_fused is not None:
                 self.opp_fused.pack()
         self.iterations = int(sd.get('iterations', 0))
         self.policy.load_state_dict(sd['policy'])
+        if 'obs_norm' in sd:
+            # restored whatever cfg.obs_norm says: the flag only decides whether it keeps updating
+            if self.obs_norm is None:
+                self._attach_obs_norm(ObsNorm(self.env.obs_dim, self.device, self.cfg.obs_norm_eps))
+            self.obs_norm.load_state_dict(sd['obs_norm'])
         self.opt.load_state_dict(sd['opt'])
         if self.fused_opt is not None:
             self.fused_opt.bind_state()

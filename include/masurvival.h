@@ -351,6 +351,56 @@ int mas_rows_select(int64_t n_envs, int32_t n_agents, uint32_t agent_mask,
                     const int8_t* actions, int8_t* actions_out, /* [rows][6] */
                     int32_t n_f32, const float* const* f32_in, float* const* f32_out,
                     void* stream);
+/* Running observation normalisation (additions within ABI version 3).  The
+ * normaliser (per-column mean and 1 / std) is never applied to a row: it is
+ * folded into the packed layer-1 weights, W1 ((x - mean) * s) + b1 =
+ * (W1 diag(s)) x + (b1 - W1 (mean * s)), so every consumer of a packed image
+ * (mas_policy_act*, mas_policy_train*) acts on raw rows unchanged.  All
+ * pointers are DEVICE pointers; every call is stream-ordered, allocates
+ * nothing, does not synchronise and can be captured; an argument error is
+ * MAS_ERR_INVALID_ARG before any device work.
+ *
+ * mas_obs_stats: sums[0][c] = sum over the rows of x[r][c], sums[1][c] = sum
+ * of x[r][c]^2, c < n_cols; sums is [2][n_cols] doubles, x_bf16 is
+ * [n_rows][x_stride] bf16 (16-B aligned, x_stride a multiple of 8, n_cols in
+ * 1..x_stride and any remainder mod 8).  Columns at or past n_cols never
+ * reach the output, whatever they hold.  Accumulated in fp64 (every term is
+ * exact) in a fixed order over a grid that depends on (n_rows, n_cols)
+ * alone: the same inputs give the same bits, whatever scratch held.  scratch:
+ * double[mas_obs_stats_scratch_doubles(n_rows, n_cols)] (-1 for n_rows < 0 or
+ * n_cols < 1), the call's partial records; concurrent calls need their own.
+ * n_rows == 0 zero-fills sums.  Refused: n_rows < 0, n_cols outside
+ * 1..x_stride, x_stride no positive multiple of 8, x_bf16 not 16-B aligned
+ * (or null with rows to read), sums or scratch null or not 8-B aligned.
+ *
+ * mas_obs_norm_merge: one batch into the running state, Chan's parallel
+ * update in fp64.  state [1 + 2 n_cols] = count, mean[], m2[]; batch
+ * [1 + 2 n_cols] = count_b, sum[], sum of squares[] (mas_obs_stats writes at
+ * batch + 1, the caller fills count_b; several ranks all-reduce the whole
+ * array first).  With n_b = count_b, n = count + n_b:
+ *   mean_b = sum / n_b,  m2_b = max(sumsq - n_b mean_b^2, 0),  d = mean_b - mean,
+ *   mean += d n_b / n,  m2 += m2_b + d^2 count n_b / n,  count = n;
+ * n_b == 0 leaves the state as it is.  Always written: mean_out[c] =
+ * (float)mean, inv_std_out[c] = (float)(1 / sqrt(m2 / count + eps)), and 0, 1
+ * (the identity) while count == 0.  eps is the only bound on inv_std
+ * (<= 1 / sqrt(eps)): the fold cannot clip a normalised value.
+ *
+ * mas_policy_pack_norm: mas_policy_pack with the fold.  The layer-1 fragment
+ * element is bf16(w1[f][k] * inv_std[k]) (an fp32 product, round to nearest
+ * even); the bias is (float)((double)b1[f] - sum_k (double)w1r[f][k] *
+ * (double)mean[k]), k ascending, w1r the ROUNDED bf16 weight -- the kernels
+ * multiply x by those, so a column that sits at its mean cancels exactly --
+ * then scaled as mas_policy_pack scales b1.  The rest of the image is
+ * mas_policy_pack's.  mean == NULL and inv_std == NULL: mas_policy_pack, byte
+ * for byte; only one of them NULL is an error. */
+int64_t mas_obs_stats_scratch_doubles(int64_t n_rows, int32_t n_cols);
+int mas_obs_stats(int64_t n_rows, int32_t n_cols, const void* x_bf16, int64_t x_stride,
+                  double* sums, double* scratch, void* stream);
+int mas_obs_norm_merge(int32_t n_cols, double* state, const double* batch, double eps,
+                       float* mean_out, float* inv_std_out, void* stream);
+int mas_policy_pack_norm(int32_t obs_dim, const float* w1, const float* b1, const float* w2,
+                         const float* b2, const float* w3, const float* b3,
+                         const float* mean, const float* inv_std, void* packed, void* stream);
 int mas_policy_train(const void* packed, int32_t obs_dim, int64_t n_rows, const void* x_bf16, int64_t x_stride,
                      const int8_t* actions, const float* old_logp, const float* adv, const float* ret, float clip,
                      float vf_coef, float ent_coef, float scale, void* h1, void* h2, void* da1, void* da2, void* dz,
