@@ -506,11 +506,13 @@ class ObsNorm:
 
 
 def gae_reference(rewards, values, dones, gamma, lam, n_agents):
-    """Plain torch fp32 restatement of mas_gae (the numerics test's reference)."""
+    """Plain torch restatement of mas_gae in the dtype of `rewards` (fp32: the
+    CPU trainer's GAE; tests/gae_ref.py holds it to fp64).  Any nonzero done
+    byte is done, as in the kernels."""
     T = rewards.shape[0]
     r = rewards.reshape(T, -1)
     v = values.reshape(T + 1, -1)
-    nt = 1.0 - dones.reshape(T, -1).float().repeat_interleave(n_agents, dim=1)
+    nt = (dones.reshape(T, -1) == 0).to(r.dtype).repeat_interleave(n_agents, dim=1)
     adv = torch.zeros_like(r)
     a = torch.zeros_like(r[0])
     for t in range(T - 1, -1, -1):

@@ -179,11 +179,17 @@ int mas_set_state(mas_handle* h, const void* src, void* stream);
  * n_columns = n_envs * n_agents agent columns, all DEVICE pointers:
  *   rewards [T][n_columns], values [T+1][n_columns] (row T = bootstrap value
  *   of the observation after the last step), done [T][n_envs] (mas_step's
- *   done; an auto-reset env's next value is masked out),
+ *   done; any nonzero byte is done, and column m reads the flag of env
+ *   m / n_agents),
  *   advantages/returns [T][n_columns] (out), adv_sums double[2] (out:
  *   sum and sum of squares of the advantages, for normalisation).
  *   delta_t = r_t + gamma * V_{t+1} * (1 - d_t) - V_t
- *   A_t     = delta_t + gamma * lambda * (1 - d_t) * A_{t+1}
+ *   A_t     = delta_t + gamma * lambda * (1 - d_t) * A_{t+1},  A_T = 0
+ *   returns_t = A_t + V_t
+ * with d_t = 1 where the byte is nonzero.  At a done step an auto-reset
+ * env's next value and the later advantages are multiplied by zero: a finite
+ * V_{t+1} or A_{t+1} drops out, a non-finite one (inf, NaN) still gives NaN
+ * and propagates to every earlier step of the column.
  * scratch: DEVICE double[mas_gae_scratch_doubles(n_columns)], the call's
  * per-workgroup partial sums (no initialisation needed; the library keeps
  * no state between calls, so calls on different streams -- or handles,
