@@ -219,11 +219,28 @@ __device__ __forceinline__ void gae_block_part(double s1, double s2, double* __r
     }
 }
 
+// mas_gae_scaled's reward (kScale): r * s, a rounding of its own (the build
+// contracts nothing), clamped to [-c, c]; a NaN fails both comparisons and
+// passes through, as torch.clamp's.  mas_gae's (!kScale) is the load itself
+template <bool kScale>
+__device__ __forceinline__ float gae_reward(float r, float s, float c)
+{
+    if constexpr (kScale) {
+        const float x = r * s;
+        return x < -c ? -c : (x > c ? c : x);
+    } else {
+        return r;
+    }
+}
+
+template <bool kScale>
 __global__ __launch_bounds__(256) void k_gae(int T, int64_t M, int A, const float* __restrict__ rew,
                                              const float* __restrict__ val, const uint8_t* __restrict__ done,
-                                             float gamma, float lam, float* __restrict__ adv,
-                                             float* __restrict__ ret, double* __restrict__ part)
+                                             float gamma, float lam, const float* __restrict__ scale_p, float clip,
+                                             float* __restrict__ adv, float* __restrict__ ret,
+                                             double* __restrict__ part)
 {
+    const float rs = kScale ? scale_p[0] : 1.0f;  // (one uniform load; the host never sees it)
     __shared__ float sr[64][kGaeCols + 1];   // rewards, then the advantages
     __shared__ float sv[65][kGaeCols + 1];   // values (the chunk's and the next step's)
     __shared__ float sn[64][kGaeCols + 1];   // 1 - done, then the returns
@@ -259,7 +276,7 @@ __global__ __launch_bounds__(256) void k_gae(int T, int64_t M, int A, const floa
                 const int q = w + 4 * k;
                 if (q <= n) sv[q][lane] = lv[k];
                 if (q < n) {
-                    sr[q][lane] = lr[k];
+                    sr[q][lane] = gae_reward<kScale>(lr[k], rs, clip);  // (after the loads: they stay back to back)
                     sn[q][lane] = ld[k] ? 0.0f : 1.0f;
                 }
             }
@@ -321,16 +338,19 @@ __global__ __launch_bounds__(256) void k_gae(int T, int64_t M, int A, const floa
 // the same partial-sum slots as k_gae
 constexpr int kGaeChunk = 8;
 
+template <bool kScale>
 __global__ __launch_bounds__(256) void k_gae_walk(int T, int64_t M, int A, const float* __restrict__ rew,
                                              const float* __restrict__ val, const uint8_t* __restrict__ done,
-                                             float gamma, float lam, float* __restrict__ adv,
-                                             float* __restrict__ ret, double* __restrict__ part)
+                                             float gamma, float lam, const float* __restrict__ scale_p, float clip,
+                                             float* __restrict__ adv, float* __restrict__ ret,
+                                             double* __restrict__ part)
 {
     const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t E = M / A;
     double s1 = 0.0, s2 = 0.0;
     if (m < M) {
         const int64_t e = m / A;
+        const float rs = kScale ? scale_p[0] : 1.0f;
         float a = 0.0f;
         float vnext = val[(int64_t)T * M + m];
         int t = T - 1;
@@ -339,7 +359,7 @@ __global__ __launch_bounds__(256) void k_gae_walk(int T, int64_t M, int A, const
 #pragma unroll
             for (int k = 0; k < kGaeChunk; ++k) {
                 const int64_t row = t - k;
-                r[k] = rew[row * M + m];
+                r[k] = gae_reward<kScale>(rew[row * M + m], rs, clip);
                 v[k] = val[row * M + m];
                 nt[k] = done[row * E + e] ? 0.0f : 1.0f;
             }
@@ -356,7 +376,7 @@ __global__ __launch_bounds__(256) void k_gae_walk(int T, int64_t M, int A, const
             }
         }
         for (; t >= 0; --t) {
-            const float r = rew[(int64_t)t * M + m], v = val[(int64_t)t * M + m];
+            const float r = gae_reward<kScale>(rew[(int64_t)t * M + m], rs, clip), v = val[(int64_t)t * M + m];
             const float nt = done[(int64_t)t * E + e] ? 0.0f : 1.0f;
             const float delta = r + gamma * vnext * nt - v;
             a = delta + gamma * lam * nt * a;
@@ -368,6 +388,52 @@ __global__ __launch_bounds__(256) void k_gae_walk(int T, int64_t M, int A, const
         }
     }
     // the workgroup's partial sums into its slot (k_gae)
+    gae_block_part(s1, s2, part);
+}
+
+// mas_ret_stats: the running discounted return of every column, forward over
+// the rollout.  One thread per column walking t = 0..T-1 from the column's
+// carry, the rows prefetched kGaeChunk steps ahead as in k_gae_walk;
+// R = fl(fl(gamma R) + r) (two roundings), (R, R^2) summed in double (both
+// exact), and only then the reset at a done step, so the step that ends an
+// episode counts (VecNormalize's order).  The workgroup's pair goes into its
+// slot of the caller's scratch and k_gae_sums adds the slots
+__global__ __launch_bounds__(256) void k_ret_stats(int T, int64_t M, int A, const float* __restrict__ rew,
+                                                   const uint8_t* __restrict__ done, float gamma,
+                                                   float* __restrict__ carry, double* __restrict__ part)
+{
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t E = M / A;
+    double s1 = 0.0, s2 = 0.0;
+    if (m < M) {
+        const int64_t e = m / A;
+        float R = carry[m];
+        int t = 0;
+        for (; t + kGaeChunk <= T; t += kGaeChunk) {
+            float r[kGaeChunk];
+            uint8_t d[kGaeChunk];
+#pragma unroll
+            for (int k = 0; k < kGaeChunk; ++k) {
+                const int64_t row = t + k;
+                r[k] = rew[row * M + m];
+                d[k] = done[row * E + e];
+            }
+#pragma unroll
+            for (int k = 0; k < kGaeChunk; ++k) {
+                R = gamma * R + r[k];
+                s1 += (double)R;
+                s2 += (double)R * (double)R;
+                if (d[k]) R = 0.0f;
+            }
+        }
+        for (; t < T; ++t) {
+            R = gamma * R + rew[(int64_t)t * M + m];
+            s1 += (double)R;
+            s2 += (double)R * (double)R;
+            if (done[(int64_t)t * E + e]) R = 0.0f;
+        }
+        carry[m] = R;
+    }
     gae_block_part(s1, s2, part);
 }
 
@@ -1072,31 +1138,75 @@ int64_t mas_gae_scratch_doubles(int64_t n_columns)
     return n_columns > 0 ? 2 * ((n_columns + kGaeCols - 1) / kGaeCols) : -1;
 }
 
-int mas_gae(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards, const float* values,
-            const uint8_t* done, float gamma, float lam, float* advantages, float* returns, double* adv_sums,
-            double* scratch, void* stream)
+namespace {
+// mas_gae and mas_gae_scaled (reward_scale non-null): the checks they share,
+// worded for `name`, and the launches
+int gae_launch(const char* name, int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards,
+               const float* values, const uint8_t* done, float gamma, float lam, const float* reward_scale,
+               float reward_clip, bool scaled, float* advantages, float* returns, double* adv_sums, double* scratch,
+               void* stream)
 {
+    const std::string nm(name);
     if (T <= 0 || n_columns <= 0 || n_agents <= 0 || n_columns % n_agents)
-        return fail(MAS_ERR_INVALID_ARG, "mas_gae: need T > 0 and n_columns a positive multiple of n_agents");
-    if (!rewards || !values || !done || !advantages || !returns || !adv_sums || !scratch)
-        return fail(MAS_ERR_INVALID_ARG, "mas_gae: null argument");
+        return fail(MAS_ERR_INVALID_ARG, nm + ": need T > 0 and n_columns a positive multiple of n_agents");
+    if (!rewards || !values || !done || !advantages || !returns || !adv_sums || !scratch || (scaled && !reward_scale))
+        return fail(MAS_ERR_INVALID_ARG, nm + ": null argument");
     if ((n_columns + kGaeCols - 1) / kGaeCols > 0x7fffffff)
-        return fail(MAS_ERR_INVALID_ARG, "mas_gae: n_columns too large");
+        return fail(MAS_ERR_INVALID_ARG, nm + ": n_columns too large");
+    if (scaled && !(reward_clip > 0.0f))
+        return fail(MAS_ERR_INVALID_ARG, nm + ": reward_clip must be positive (+inf: no clipping)");
     hipStream_t s = (hipStream_t)stream;
     // the per-column walk (default); MAS_GAE_SCAN=1: the wavefront scan over
     // time (measured 135 vs 61.5 us at T = 64, 65536 x 4 columns)
     const char* scan_env = getenv("MAS_GAE_SCAN");
-    int nblocks;
-    if (scan_env && scan_env[0] == '1') {
-        nblocks = (int)((n_columns + kGaeCols - 1) / kGaeCols);
-        hipLaunchKernelGGL(k_gae, dim3((unsigned)nblocks), dim3(256), 0, s, (int)T, (int64_t)n_columns, (int)n_agents,
-                           rewards, values, done, gamma, lam, advantages, returns, scratch);
-    } else {
-        nblocks = (int)((n_columns + kGaeWalkCols - 1) / kGaeWalkCols);
-        hipLaunchKernelGGL(k_gae_walk, dim3((unsigned)nblocks), dim3(256), 0, s, (int)T, (int64_t)n_columns,
-                           (int)n_agents, rewards, values, done, gamma, lam, advantages, returns, scratch);
-    }
+    const bool scan = scan_env && scan_env[0] == '1';
+    const int nblocks = (int)((n_columns + (scan ? kGaeCols : kGaeWalkCols) - 1) / (scan ? kGaeCols : kGaeWalkCols));
+    auto* kern = scan ? (scaled ? k_gae<true> : k_gae<false>) : (scaled ? k_gae_walk<true> : k_gae_walk<false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), 0, s, (int)T, (int64_t)n_columns, (int)n_agents,
+                       rewards, values, done, gamma, lam, reward_scale, reward_clip, advantages, returns, scratch);
     hipLaunchKernelGGL(k_gae_sums, dim3(1), dim3(256), 0, s, (const double*)scratch, nblocks, adv_sums);
+    HIP_TRY(hipGetLastError());
+    return MAS_OK;
+}
+}  // namespace
+
+int mas_gae(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards, const float* values,
+            const uint8_t* done, float gamma, float lam, float* advantages, float* returns, double* adv_sums,
+            double* scratch, void* stream)
+{
+    return gae_launch("mas_gae", T, n_columns, n_agents, rewards, values, done, gamma, lam, nullptr, 0.0f, false,
+                      advantages, returns, adv_sums, scratch, stream);
+}
+
+int mas_gae_scaled(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards, const float* values,
+                   const uint8_t* done, float gamma, float lam, const float* reward_scale, float reward_clip,
+                   float* advantages, float* returns, double* adv_sums, double* scratch, void* stream)
+{
+    return gae_launch("mas_gae_scaled", T, n_columns, n_agents, rewards, values, done, gamma, lam, reward_scale,
+                      reward_clip, true, advantages, returns, adv_sums, scratch, stream);
+}
+
+int64_t mas_ret_stats_scratch_doubles(int64_t n_columns)
+{
+    return n_columns > 0 ? 2 * ((n_columns + kGaeWalkCols - 1) / kGaeWalkCols) : -1;
+}
+
+int mas_ret_stats(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards, const uint8_t* done,
+                  float gamma, float* ret_carry, double* sums, double* scratch, void* stream)
+{
+    if (T <= 0 || n_columns <= 0 || n_agents <= 0 || n_columns % n_agents)
+        return fail(MAS_ERR_INVALID_ARG,
+                    "mas_ret_stats: need T > 0 and n_columns a positive multiple of n_agents");
+    if (!rewards || !done || !ret_carry || !sums || !scratch)
+        return fail(MAS_ERR_INVALID_ARG, "mas_ret_stats: null argument");
+    if ((n_columns + kGaeWalkCols - 1) / kGaeWalkCols > 0x7fffffff)
+        return fail(MAS_ERR_INVALID_ARG, "mas_ret_stats: n_columns too large");
+    if (!std::isfinite(gamma)) return fail(MAS_ERR_INVALID_ARG, "mas_ret_stats: gamma must be finite");
+    hipStream_t s = (hipStream_t)stream;
+    const int nblocks = (int)((n_columns + kGaeWalkCols - 1) / kGaeWalkCols);
+    hipLaunchKernelGGL(k_ret_stats, dim3((unsigned)nblocks), dim3(256), 0, s, (int)T, (int64_t)n_columns,
+                       (int)n_agents, rewards, done, gamma, ret_carry, scratch);
+    hipLaunchKernelGGL(k_gae_sums, dim3(1), dim3(256), 0, s, (const double*)scratch, nblocks, sums);
     HIP_TRY(hipGetLastError());
     return MAS_OK;
 }

@@ -48,6 +48,16 @@ again, so rollout k and update k see one normaliser (the reset rows are
 counted twice, once in a lifetime: as block 0 of the first rollout too).
 Nothing clips a normalised value: ``obs_norm_eps`` (the variance floor) is the
 only bound, ``inv_std <= 1 / sqrt(eps)`` (10 by default).
+
+Reward normalisation (``PPOConfig.reward_norm``): VecNormalize's other half.
+Every agent column keeps a running discounted return R across rollouts
+(``RetNorm.carry``); after a rollout (and the learner's row selection)
+``mas_ret_stats`` walks it forward and sums R and R^2 in fp64, the record is
+all-reduced and merged (Chan, ``mas_obs_norm_merge`` with one column), and GAE
+(``mas_gae_scaled``) reads ``clamp(r * scale, -reward_clip, reward_clip)`` with
+``scale = 1 / sqrt(var(R) + reward_norm_eps)`` from device memory.  The rollout's
+own returns are merged before its rewards are scaled; the mean is not
+subtracted; the rewards buffer keeps the raw rewards.
 """
 from __future__ import annotations
 
@@ -123,6 +133,13 @@ class PPOConfig:
     # fold cannot clip a normalised value (VecNormalize clips at +-10), so
     # this alone bounds how far a near-constant column is amplified
     obs_norm_eps: float = 1e-2
+    # running return normalisation of the rewards (module docstring): GAE reads
+    # clamp(r / sqrt(var(R) + reward_norm_eps), -reward_clip, reward_clip), R the
+    # columns' running discounted returns; off: the same launches and bits as
+    # without it
+    reward_norm: bool = False
+    reward_norm_eps: float = 1e-8
+    reward_clip: float = 10.0
 
 
 def _split_k(m: int, cap: int = int(os.environ.get('MAS_SPLITK_CAP', '128'))) -> int:
@@ -282,6 +299,81 @@ def adv_normalize(adv, stats, stream=None):
     st = stream if stream is not None else torch.cuda.current_stream(adv.device).cuda_stream
     check(lib.mas_adv_normalize(adv.numel(), ctypes.c_void_p(adv.data_ptr()), ctypes.c_void_p(stats.data_ptr()),
                                 ctypes.c_void_p(st)))
+
+
+def _rollout_columns(name, rewards, dones, n_agents):
+    """(T, M) of a [T, ..] fp32 rewards tensor and its [T, envs] uint8 dones on one GPU, or ValueError."""
+    if not (isinstance(rewards, torch.Tensor) and rewards.is_cuda and rewards.dtype == torch.float32
+            and rewards.dim() >= 2 and rewards.is_contiguous()):
+        raise ValueError(f'{name}: rewards must be a contiguous fp32 [T, columns] tensor on a GPU')
+    T, M = rewards.shape[0], rewards[0].numel()
+    if not (isinstance(dones, torch.Tensor) and dones.device == rewards.device and dones.dtype == torch.uint8
+            and dones.is_contiguous() and dones.dim() >= 1 and dones.shape[0] == T
+            and dones[0].numel() * int(n_agents) == M):
+        raise ValueError(f'{name}: dones must be a contiguous uint8 [T, columns / n_agents] tensor beside the rewards')
+    return T, M
+
+
+def ret_stats(rewards, dones, gamma, carry, sums_out, n_agents, stream=None, scratch=None):
+    """HIP running-return statistics over [T, N*A] columns (include/masurvival.h
+    mas_ret_stats): carry (fp32 [N*A], each column's discounted return so far)
+    is advanced in place through the rollout and sums_out (fp64 [2]) receives
+    the sum of the T * N*A returns and of their squares.  scratch: float64
+    device tensor of mas_ret_stats_scratch_doubles(N*A) (a gae_scratch is large
+    enough; allocated here when None)."""
+    lib = load_library()
+    if not hasattr(lib, 'mas_ret_stats'):
+        raise MasError('the loaded library has no mas_ret_stats')
+    T, M = _rollout_columns('ret_stats', rewards, dones, n_agents)
+    dev = rewards.device
+    if not (carry.device == dev and carry.dtype == torch.float32 and carry.is_contiguous() and carry.numel() == M):
+        raise ValueError(f'ret_stats: carry must be a contiguous fp32 tensor of {M} columns on {dev}')
+    if not (sums_out.device == dev and sums_out.dtype == torch.float64 and sums_out.is_contiguous()
+            and sums_out.numel() == 2):
+        raise ValueError('ret_stats: sums_out must be a contiguous fp64 [2] tensor beside the rewards')
+    need = int(lib.mas_ret_stats_scratch_doubles(M))
+    if scratch is None:
+        scratch = torch.empty((need,), device=dev, dtype=torch.float64)
+    if not (scratch.device == dev and scratch.dtype == torch.float64 and scratch.numel() >= need):
+        raise ValueError(f'ret_stats: scratch must hold {need} fp64 values on {dev}')
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    check(lib.mas_ret_stats(T, M, int(n_agents), ctypes.c_void_p(rewards.data_ptr()),
+                            ctypes.c_void_p(dones.data_ptr()), float(gamma), ctypes.c_void_p(carry.data_ptr()),
+                            ctypes.c_void_p(sums_out.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+                            ctypes.c_void_p(s)))
+
+
+def gae_scaled(rewards, values, dones, gamma, lam, scale, clip, adv_out, ret_out, sums_out, n_agents, stream=None,
+               scratch=None):
+    """gae() on clamp(rewards * scale, -clip, clip) without writing the rewards
+    (include/masurvival.h mas_gae_scaled).  scale: fp32 [1] DEVICE tensor, read
+    by the kernel (no host copy); clip: a positive float, inf for none."""
+    lib = load_library()
+    if not hasattr(lib, 'mas_gae_scaled'):
+        raise MasError('the loaded library has no mas_gae_scaled')
+    T = rewards.shape[0]
+    M = rewards[0].numel()
+    for t in (rewards, values, adv_out, ret_out):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    assert values.shape[0] == T + 1 and dones.shape[0] == T and dones.dtype == torch.uint8
+    assert dones[0].numel() * n_agents == M and sums_out.dtype == torch.float64
+    assert scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1
+    if scratch is None:
+        scratch = gae_scratch(M, rewards.device)
+    assert scratch.is_cuda and scratch.dtype == torch.float64 and scratch.numel() >= lib.mas_gae_scratch_doubles(M)
+    s = stream if stream is not None else torch.cuda.current_stream(rewards.device).cuda_stream
+    check(lib.mas_gae_scaled(T, M, n_agents, ctypes.c_void_p(rewards.data_ptr()), ctypes.c_void_p(values.data_ptr()),
+                             ctypes.c_void_p(dones.data_ptr()), float(gamma), float(lam),
+                             ctypes.c_void_p(scale.data_ptr()), float(clip),
+                             ctypes.c_void_p(adv_out.data_ptr()), ctypes.c_void_p(ret_out.data_ptr()),
+                             ctypes.c_void_p(sums_out.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+                             ctypes.c_void_p(s)))
+
+
+def scale_rewards_reference(rewards, scale, clip):
+    """Plain torch restatement of mas_gae_scaled's reward: the fp32 product,
+    rounded on its own, then the clamp (a NaN passes through)."""
+    return torch.clamp(rewards * scale.to(rewards.dtype), -float(clip), float(clip))
 
 
 def _agent_mask(agents, n_agents, what='agents'):
@@ -503,6 +595,129 @@ class ObsNorm:
         on = cls(sd['mean'].numel(), device, sd.get('eps', 1e-2))
         on.load_state_dict(sd)
         return on
+
+
+def ret_stats_reference(rewards, dones, gamma, carry, n_agents, steps_out=None):
+    """Plain torch restatement of mas_ret_stats in fp32 (the CPU trainer's;
+    tests/ret_ref.py holds it to fp64): returns (the new carry [columns], the
+    fp64 sums [2] of the T * columns running returns and of their squares).
+    Per step R = fl32(fl32(gamma * R) + r) (two torch ops, so two roundings),
+    R and R^2 counted in double, then R = 0 where the column's env is done (any
+    nonzero byte).  `carry` is not written.  steps_out: an optional [T, columns]
+    tensor that receives every step's R as it was counted."""
+    T = rewards.shape[0]
+    r = rewards.reshape(T, -1)
+    d = (dones.reshape(T, -1) != 0).repeat_interleave(int(n_agents), dim=1)
+    g = torch.tensor(float(gamma), dtype=r.dtype, device=r.device)
+    R = carry.reshape(-1).to(r.dtype).clone()
+    sums = torch.zeros((2,), dtype=torch.float64, device=r.device)
+    for t in range(T):
+        R = R * g
+        R = R + r[t]
+        Rd = R.to(torch.float64)
+        sums[0] += Rd.sum()
+        sums[1] += (Rd * Rd).sum()
+        if steps_out is not None:
+            steps_out[t].copy_(R.reshape(steps_out[t].shape))
+        R = torch.where(d[t], torch.zeros_like(R), R)
+    return R, sums
+
+
+class RetNorm:
+    """Running variance of the discounted returns (VecNormalize's reward half,
+    batched per rollout): the fp64 state (count, mean, m2) of every step's
+    running return R, the fp32 per-column ``carry`` of R across rollouts, and
+    the fp32 ``scale`` [1] = 1 / sqrt(m2 / count + eps) made from the state (1
+    while the count is 0), all on `device`.  The mean is kept for the variance
+    and never subtracted from a reward.  On a GPU ``update`` is mas_ret_stats +
+    mas_obs_norm_merge with one column (include/masurvival.h); elsewhere the
+    torch restatement (ret_stats_reference, merge_reference).  ``scale`` is
+    updated in place and read on the device by mas_gae_scaled."""
+
+    def __init__(self, n_columns, device, eps=1e-8):
+        self.n_columns, self.device, self.eps = int(n_columns), torch.device(device), float(eps)
+        self.state = torch.zeros((3,), dtype=torch.float64, device=self.device)
+        self.batch = torch.zeros_like(self.state)
+        self.carry = torch.zeros((self.n_columns,), dtype=torch.float32, device=self.device)
+        self.scale = torch.ones((1,), dtype=torch.float32, device=self.device)
+        self._mean32 = torch.zeros((1,), dtype=torch.float32, device=self.device)  # the merge's other output
+        self._scratch = None
+        self.lib = None
+        if self.device.type == 'cuda':
+            self.lib = load_library()
+            if not hasattr(self.lib, 'mas_ret_stats') or not hasattr(self.lib, 'mas_obs_norm_merge'):
+                raise MasError('the loaded library has no mas_ret_stats / mas_obs_norm_merge')
+
+    @property
+    def count(self):
+        return self.state[0]
+
+    def _merge(self, group, reduce):
+        if reduce:
+            dist.all_reduce(self.batch, group=group)
+        if self.lib is not None:
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+            check(self.lib.mas_obs_norm_merge(1, ptr(self.state), ptr(self.batch), self.eps, ptr(self._mean32),
+                                              ptr(self.scale),
+                                              ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        else:
+            self.scale.copy_(merge_reference(self.state, self.batch, self.eps)[1])
+
+    @torch.no_grad()
+    def update(self, rewards, dones, n_agents, gamma, group=None, reduce=None, scratch=None):
+        """Advance the carry through the rollout (rewards fp32 [T, columns..],
+        dones uint8 [T, envs], column m of env m // n_agents) and merge its
+        T * columns running returns into the state; `rewards` is only read.
+        reduce (default: whether a group is given): all-reduce the batch
+        record (count, sum, sum of squares) over `group` first, so every rank
+        ends with the same state and scale (the carries stay per rank).
+        scratch: a GPU caller's fp64 scratch to share (a gae_scratch of the
+        same columns), for calls ordered on one stream."""
+        T = rewards.shape[0]
+        if rewards[0].numel() != self.n_columns or rewards.device.type != self.device.type:
+            raise ValueError(f'RetNorm.update: need rewards of {self.n_columns} columns on {self.device}, got '
+                             f'{tuple(rewards.shape)} on {rewards.device}')
+        self.batch[:1].fill_(float(T * self.n_columns))  # (the all-reduce sums the ranks' counts in place)
+        if self.lib is not None:
+            if scratch is None:
+                if self._scratch is None:
+                    need = int(self.lib.mas_ret_stats_scratch_doubles(self.n_columns))
+                    self._scratch = torch.empty((need,), dtype=torch.float64, device=self.device)
+                scratch = self._scratch
+            ret_stats(rewards, dones, gamma, self.carry, self.batch[1:], n_agents, scratch=scratch)
+        else:
+            carry, sums = ret_stats_reference(rewards, dones, gamma, self.carry, n_agents)
+            self.carry.copy_(carry)
+            self.batch[1:].copy_(sums)
+        self._merge(group, group is not None if reduce is None else reduce)
+
+    @torch.no_grad()
+    def refresh(self):
+        """scale again from the state (a merge of an empty batch)."""
+        self.batch.zero_()
+        self._merge(None, False)
+
+    def state_dict(self):
+        return {'count': self.state[0].detach().clone(), 'mean': self.state[1].detach().clone(),
+                'm2': self.state[2].detach().clone(), 'eps': float(self.eps), 'carry': self.carry.detach().clone()}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if tuple(sd['carry'].shape) != (self.n_columns,):
+            raise ValueError(f'RetNorm: checkpoint carry of shape {tuple(sd["carry"].shape)}, expected '
+                             f'({self.n_columns},)')
+        self.state[0] = sd['count'].to(torch.float64)
+        self.state[1] = sd['mean'].to(torch.float64)
+        self.state[2] = sd['m2'].to(torch.float64)
+        self.carry.copy_(sd['carry'])
+        self.eps = float(sd.get('eps', self.eps))
+        self.refresh()
+
+    @classmethod
+    def from_state_dict(cls, sd, device):
+        rn = cls(sd['carry'].numel(), device, sd.get('eps', 1e-8))
+        rn.load_state_dict(sd)
+        return rn
 
 
 def gae_reference(rewards, values, dones, gamma, lam, n_agents):
@@ -1127,6 +1342,15 @@ class PPOTrainer:
         self.obs_norm = None
         if cfg.obs_norm:
             self._attach_obs_norm(ObsNorm(env.obs_dim, self.device, cfg.obs_norm_eps))
+        # the reward normaliser (RetNorm) over the columns GAE reads (with
+        # self-play the learner's); also made by load_state_dict from a
+        # checkpoint that has one.  Its scale is applied whenever it exists;
+        # cfg.reward_norm only decides whether it keeps updating
+        self.ret_norm = None
+        if cfg.reward_norm:
+            if not (cfg.reward_clip > 0):
+                raise ValueError(f'PPOConfig.reward_clip must be positive (inf: no clipping), got {cfg.reward_clip}')
+            self.ret_norm = RetNorm(self._gae_columns(), self.device, cfg.reward_norm_eps)
         fused = cfg.fused
         if fused is None:
             fused = self.device.type == 'cuda' and cfg.hidden == 256
@@ -1162,6 +1386,11 @@ class PPOTrainer:
             self._sync_rollout_policy()
         if self.learner_agents is not None:
             self._init_selfplay()
+
+    def _gae_columns(self):
+        """Agent columns of the buffer GAE reads: every agent's, with self-play the learner's."""
+        A = self.env.n_agents if self.learner_agents is None else len(self.learner_agents)
+        return int(self.env.n_envs) * int(A)
 
     def _attach_obs_norm(self, on):
         self.obs_norm = on
@@ -1433,8 +1662,23 @@ class PPOTrainer:
             b = b.learner
         if self.gae_impl is gae and b.gae_scratch is None:
             b.gae_scratch = gae_scratch(b.N * b.A, self.device)
-        self.gae_impl(b.rewards, b.values, b.dones, c.gamma, c.lam, b.adv, b.ret, b.adv_sums, b.A,
+        rn = self.ret_norm
+        if rn is not None and c.reward_norm:
+            # this rollout's running returns into the statistics before its rewards are scaled (as
+            # VecNormalize updates before it normalises); the calls share the GAE scratch: one stream
+            rn.update(b.rewards, b.dones, b.A, c.gamma, group=self.group, reduce=self.collectives,
                       scratch=b.gae_scratch)
+        if rn is None:
+            self.gae_impl(b.rewards, b.values, b.dones, c.gamma, c.lam, b.adv, b.ret, b.adv_sums, b.A,
+                          scratch=b.gae_scratch)
+        elif self.gae_impl is gae:
+            # the scale applied where GAE loads the reward, read from device memory; b.rewards stays raw
+            gae_scaled(b.rewards, b.values, b.dones, c.gamma, c.lam, rn.scale, c.reward_clip, b.adv, b.ret,
+                       b.adv_sums, b.A, scratch=b.gae_scratch)
+        else:
+            # the CPU path and the injected test double: the kernel's two fp32 steps on a copy
+            self.gae_impl(scale_rewards_reference(b.rewards, rn.scale, c.reward_clip), b.values, b.dones, c.gamma,
+                          c.lam, b.adv, b.ret, b.adv_sums, b.A, scratch=b.gae_scratch)
         stats = b.adv_stats  # (b.adv_sums is its first two entries)
         if b.active is not None:
             # the statistics over the active rows: (sum w adv, sum w adv^2, sum w) in double (w is 0 or 1);
@@ -1493,6 +1737,8 @@ class PPOTrainer:
                            'clipfrac': cf.detach()}
         if share is not None:
             self.last_stats['active'] = share
+        if c.reward_norm:
+            self.last_stats['reward_scale'] = self.ret_norm.scale[0].clone()
         if c.obs_norm:
             self._obs_norm_after_update()
             self.fused.pack()
@@ -1533,6 +1779,8 @@ class PPOTrainer:
         self.last_stats = {'loss': loss.detach(), 'pg': pg.detach(), 'v': vl.detach()}
         if share is not None:
             self.last_stats['active'] = share[0]
+        if c.reward_norm:
+            self.last_stats['reward_scale'] = self.ret_norm.scale[0].clone()
         if c.obs_norm:
             self._obs_norm_after_update()
         self._sync_rollout_policy()
@@ -1554,6 +1802,8 @@ class PPOTrainer:
             sd['xb0'] = self.buf.xb[0].detach().clone()  # (x_obs: the next rollout's rows; obs0 is the reset's)
         if self.obs_norm is not None:
             sd['obs_norm'] = self.obs_norm.state_dict()  # three fp64 tensors and eps (match.load_policy reads it)
+        if self.ret_norm is not None:
+            sd['ret_norm'] = self.ret_norm.state_dict()  # count, mean, m2 (fp64), eps and the columns' carry
         if self.learner_agents is not None:
             # self-play: 'policy' stays the learner (match.load_policy reads it as any checkpoint's)
             sd['learner_agents'] = [int(a) for a in self.learner_agents]
@@ -1593,6 +1843,12 @@ class PPOTrainer:
             if self.obs_norm is None:
                 self._attach_obs_norm(ObsNorm(self.env.obs_dim, self.device, self.cfg.obs_norm_eps))
             self.obs_norm.load_state_dict(sd['obs_norm'])
+        if 'ret_norm' in sd:
+            # restored (and its scale applied) whatever cfg.reward_norm says; a checkpoint without one
+            # leaves a flagged trainer's fresh statistics as they are
+            if self.ret_norm is None:
+                self.ret_norm = RetNorm(self._gae_columns(), self.device, self.cfg.reward_norm_eps)
+            self.ret_norm.load_state_dict(sd['ret_norm'])
         self.opt.load_state_dict(sd['opt'])
         if self.fused_opt is not None:
             self.fused_opt.bind_state()

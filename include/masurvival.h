@@ -203,6 +203,49 @@ int64_t mas_gae_scratch_doubles(int64_t n_columns);
 int mas_gae(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards, const float* values,
             const uint8_t* done, float gamma, float lam, float* advantages, float* returns, double* adv_sums,
             double* scratch, void* stream);
+/* Running return normalisation of the rewards (additions within ABI version
+ * 3; VecNormalize's reward half, batched per rollout).  All pointers are
+ * DEVICE pointers; both calls are stream-ordered, allocate nothing, do not
+ * synchronise and can be captured; an argument error is MAS_ERR_INVALID_ARG
+ * before any device work.
+ *
+ * mas_ret_stats: every column m keeps a running discounted return
+ * ret_carry[m] (fp32, in/out: it persists across rollouts, 0 at the start).
+ * Step t = 0..T-1 of the rollout does, in this order,
+ *   R = fl32(fl32(gamma * R) + rewards[t][m])      two roundings, no fma
+ *   sums[0] += R,  sums[1] += R^2                  in double: both terms exact
+ *   if done[t][m / n_agents] != 0: R = 0           after the step has counted
+ * and sums [2] receives the two totals over all T * n_columns steps (written,
+ * not added to).  Every column counts.  scratch:
+ * double[mas_ret_stats_scratch_doubles(n_columns)] (-1 for n_columns < 1; never
+ * more than mas_gae_scratch_doubles(n_columns), so a GAE scratch serves calls
+ * ordered on one stream), the call's per-workgroup partial sums, summed in a
+ * fixed order: the same inputs give the same bits, whatever scratch held.
+ * Refused: T < 1, n_columns no positive multiple of n_agents, a null pointer,
+ * n_columns too large for the grid, gamma not finite.
+ *
+ * The batch record (T * n_columns, sums[0], sums[1]) merges into a running
+ * (count, mean, m2) through mas_obs_norm_merge(1, ...), whose inv_std output
+ * is the reward scale (float)(1 / sqrt(m2 / count + eps)); the mean is not
+ * subtracted from a reward.
+ *
+ * mas_gae_scaled: mas_gae (either form, MAS_GAE_SCAN read per call) on
+ *   r' = clamp(fl32(r * reward_scale[0]), -reward_clip, reward_clip)
+ * in place of r: the product is rounded on its own, x < -c ? -c : (x > c ? c : x)
+ * lets a NaN through as torch.clamp does, and the scale is read on the device
+ * from reward_scale (float[1]), so no host copy orders the call after the
+ * merge that wrote it.  rewards itself is not written.  With a scale of 1 and
+ * a clip of +inf the results are mas_gae's bit for bit.  Refused besides
+ * mas_gae's refusals: a null reward_scale, reward_clip NaN or <= 0 (+inf is
+ * allowed). */
+int64_t mas_ret_stats_scratch_doubles(int64_t n_columns);
+int mas_ret_stats(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards,
+                  const uint8_t* done, float gamma, float* ret_carry /* [n_columns], in/out */,
+                  double* sums /* [2] */, double* scratch, void* stream);
+int mas_gae_scaled(int32_t T, int64_t n_columns, int32_t n_agents, const float* rewards,
+                   const float* values, const uint8_t* done, float gamma, float lam,
+                   const float* reward_scale /* DEVICE float[1] */, float reward_clip,
+                   float* advantages, float* returns, double* adv_sums, double* scratch, void* stream);
 /* mas_adv_normalize: the n advantages (DEVICE float, 16-B aligned)
  * normalised in place from stats = DEVICE double[3] (sum, sum of squares,
  * count: mas_gae's adv_sums and the count, summed over ranks):
