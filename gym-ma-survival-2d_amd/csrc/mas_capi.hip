@@ -65,6 +65,12 @@ hipError_t obs_norm_merge(int n_cols, double* state, const double* batch, double
 hipError_t policy_pack_norm(int D, const float* W1, const float* b1, const float* W2, const float* b2,
                             const float* W3, const float* b3, const float* mean, const float* inv_std, void* packed,
                             hipStream_t s);
+// episode statistics of a rollout (mas_epstats.hip)
+int episode_stats_max_agents();
+int64_t episode_stats_blocks(int64_t n_envs);
+hipError_t episode_stats(int T, int64_t n_envs, int n_agents, uint32_t side_mask, const float* rewards,
+                         const uint8_t* done, double* ret_carry, int32_t* len_carry, double* record, double* scratch,
+                         hipStream_t s);
 }  // namespace mas
 
 namespace {
@@ -1208,6 +1214,36 @@ int mas_ret_stats(int32_t T, int64_t n_columns, int32_t n_agents, const float* r
                        (int)n_agents, rewards, done, gamma, ret_carry, scratch);
     hipLaunchKernelGGL(k_gae_sums, dim3(1), dim3(256), 0, s, (const double*)scratch, nblocks, sums);
     HIP_TRY(hipGetLastError());
+    return MAS_OK;
+}
+
+int64_t mas_episode_stats_scratch_doubles(int64_t n_envs, int32_t n_agents)
+{
+    if (n_envs <= 0 || n_agents < 1 || n_agents > episode_stats_max_agents()) return -1;
+    const int64_t nblocks = episode_stats_blocks(n_envs);
+    return nblocks > 0x7fffffff ? -1 : (6 + 2 * (int64_t)n_agents) * nblocks;
+}
+
+int mas_episode_stats(int32_t T, int64_t n_envs, int32_t n_agents, uint32_t side_mask, const float* rewards,
+                      const uint8_t* done, double* ret_carry, int32_t* len_carry, double* record, double* scratch,
+                      void* stream)
+{
+    // every check before any HIP call: the shape, then the pointers, then the grid
+    if (T <= 0) return fail(MAS_ERR_INVALID_ARG, "mas_episode_stats: need T > 0");
+    if (n_envs <= 0) return fail(MAS_ERR_INVALID_ARG, "mas_episode_stats: need n_envs > 0");
+    if (n_agents < 1) return fail(MAS_ERR_INVALID_ARG, "mas_episode_stats: need n_agents >= 1");
+    if (n_agents < 32 && (side_mask >> n_agents) != 0)
+        return fail(MAS_ERR_INVALID_ARG, "mas_episode_stats: side_mask has a bit at or above n_agents");
+    if (!rewards || !done || !ret_carry || !len_carry || !record || !scratch)
+        return fail(MAS_ERR_INVALID_ARG, "mas_episode_stats: null argument");
+    if (episode_stats_blocks(n_envs) > 0x7fffffff)
+        return fail(MAS_ERR_INVALID_ARG, "mas_episode_stats: n_envs too large");
+    if (n_agents > episode_stats_max_agents())
+        return fail(MAS_ERR_UNSUPPORTED, "mas_episode_stats: n_agents above " +
+                                             std::to_string(episode_stats_max_agents()) +
+                                             " (the kernel keeps an env's returns in registers)");
+    HIP_TRY(episode_stats((int)T, n_envs, (int)n_agents, side_mask, rewards, done, ret_carry, len_carry, record,
+                          scratch, (hipStream_t)stream));
     return MAS_OK;
 }
 

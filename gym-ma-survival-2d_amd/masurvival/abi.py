@@ -77,6 +77,9 @@ SIGNATURES = {
                                 c_void_p]),
     'mas_gae_scaled': (c_int32, [c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,
                                  c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'mas_episode_stats_scratch_doubles': (c_int64, [c_int64, c_int32]),
+    'mas_episode_stats': (c_int32, [c_int32, c_int64, c_int32, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
     'mas_debug_counters': (c_int32, [c_void_p, POINTER(c_int64)]),
     'mas_debug_guards': (c_int32, [c_void_p, POINTER(c_int64)]),
     'mas_debug_force_general': (c_int32, [c_void_p, c_int32]),
@@ -126,7 +129,8 @@ SIGNATURES = {
 # variant loaded through MAS_LIB) may lack; their callers test with hasattr
 OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel', 'mas_rows_select', 'mas_alive', 'mas_policy_train_w',
             'mas_policy_train_dw3_w', 'mas_obs_stats_scratch_doubles', 'mas_obs_stats', 'mas_obs_norm_merge',
-            'mas_policy_pack_norm', 'mas_ret_stats_scratch_doubles', 'mas_ret_stats', 'mas_gae_scaled'}
+            'mas_policy_pack_norm', 'mas_ret_stats_scratch_doubles', 'mas_ret_stats', 'mas_gae_scaled',
+            'mas_episode_stats_scratch_doubles', 'mas_episode_stats'}
 
 MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 

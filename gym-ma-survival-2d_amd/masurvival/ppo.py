@@ -58,6 +58,18 @@ all-reduced and merged (Chan, ``mas_obs_norm_merge`` with one column), and GAE
 ``scale = 1 / sqrt(var(R) + reward_norm_eps)`` from device memory.  The rollout's
 own returns are merged before its rewards are scaled; the mean is not
 subtracted; the rewards buffer keeps the raw rewards.
+
+Episode statistics (``PPOConfig.episode_stats``): what the rollouts' own
+episodes looked like.  After a rollout, before the learner's row selection,
+``mas_episode_stats`` walks the whole buffer's rewards and dones forward, one
+thread per env, from per-env carries of every agent's undiscounted return and
+of the episode length (``EpisodeStats``), and leaves one fp64 record: episodes
+finished, sums of their lengths and of every agent slot's return (and of the
+squares), wins per side and draws by Match's rule.  The record is all-reduced,
+added to a lifetime total, and ``last_stats`` gains ``episodes``,
+``ep_length``, ``ep_return`` and ``win_rate`` as device tensors;
+``episode_summary()`` is the only host copy.  Side 0 is the learner's agents
+when there is an opponent, otherwise agents ``range(A // 2)``.
 """
 from __future__ import annotations
 
@@ -140,6 +152,11 @@ class PPOConfig:
     reward_norm: bool = False
     reward_norm_eps: float = 1e-8
     reward_clip: float = 10.0
+    # episode statistics of the training rollouts (module docstring): returns,
+    # lengths and wins of the episodes each rollout finished, kept on the
+    # device; it only reads the buffer.  Off: the same launches and bits as
+    # without it
+    episode_stats: bool = False
 
 
 def _split_k(m: int, cap: int = int(os.environ.get('MAS_SPLITK_CAP', '128'))) -> int:
@@ -718,6 +735,224 @@ class RetNorm:
         rn = cls(sd['carry'].numel(), device, sd.get('eps', 1e-8))
         rn.load_state_dict(sd)
         return rn
+
+
+# the steps mas_episode_stats loads ahead of its recurrence in the default build
+# (csrc/mas_epstats.hip MAS_EP_CHUNK).  Nothing computes with it: its tests place
+# their rollout lengths around it, and under another chunk they only miss those edges
+EPISODE_STATS_CHUNK = 8
+# the record's integer entries, then sum_G[A] and sum_G2[A]
+EPISODE_RECORD_HEAD = ('episodes', 'sum_len', 'sum_len2', 'wins0', 'wins1', 'draws')
+
+
+def episode_stats_geometry():
+    """(envs per workgroup, most agents per env) of mas_episode_stats in the
+    loaded library, read off mas_episode_stats_scratch_doubles: 6 + 2A doubles
+    per workgroup, -1 for an agent count the kernel does not take."""
+    f = load_library().mas_episode_stats_scratch_doubles
+    wg = 64
+    while f(wg + 64, 1) == f(64, 1):
+        wg += 64
+    agents = 1
+    while f(1, agents + 1) >= 0:
+        agents += 1
+    return wg, agents
+
+
+def _episode_side_mask(side_mask, n_agents):
+    m, A = int(side_mask), int(n_agents)
+    if A < 1 or m < 0 or (m >> A) != 0:
+        raise ValueError(f'episode statistics: side_mask {side_mask!r} has a bit at or above n_agents {n_agents}')
+    return m
+
+
+def _episode_stats_call(name, rewards, dones, n_agents, ret_carry, len_carry, record_out, side_mask, stream, scratch):
+    """The checked mas_episode_stats call: its return code (ValueError for a wrong tensor first)."""
+    lib = load_library()
+    if not hasattr(lib, 'mas_episode_stats'):
+        raise MasError('the loaded library has no mas_episode_stats')
+    A = int(n_agents)
+    mask = _episode_side_mask(side_mask, A)
+    T, M = _rollout_columns(name, rewards, dones, A)
+    E, dev = M // A, rewards.device
+    for what, t, dtype, n in (('ret_carry', ret_carry, torch.float64, M), ('len_carry', len_carry, torch.int32, E),
+                              ('record_out', record_out, torch.float64, len(EPISODE_RECORD_HEAD) + 2 * A)):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and t.is_contiguous()
+                and t.numel() == n):
+            raise ValueError(f'{name}: {what} must be a contiguous {dtype} tensor of {n} values on {dev}')
+    need = int(lib.mas_episode_stats_scratch_doubles(E, A))
+    if need < 0:
+        raise ValueError(f'{name}: the kernel does not take {E} envs of {A} agents (episode_stats_reference does)')
+    if scratch is None:
+        scratch = torch.empty((need,), device=dev, dtype=torch.float64)
+    if not (isinstance(scratch, torch.Tensor) and scratch.device == dev and scratch.dtype == torch.float64
+            and scratch.is_contiguous() and scratch.numel() >= need):
+        raise ValueError(f'{name}: scratch must hold {need} fp64 values on {dev}')
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    return lib.mas_episode_stats(T, E, A, mask, ptr(rewards), ptr(dones), ptr(ret_carry), ptr(len_carry),
+                                 ptr(record_out), ptr(scratch), ctypes.c_void_p(s))
+
+
+def episode_stats(rewards, dones, n_agents, ret_carry, len_carry, record_out, side_mask=0, stream=None, scratch=None):
+    """HIP episode statistics of a rollout (include/masurvival.h
+    mas_episode_stats): rewards fp32 [T, N*A..] and dones uint8 [T, N] are
+    walked forward per env from ret_carry (fp64 [N*A], each agent's return in
+    the episode so far) and len_carry (int32 [N], its length so far), both
+    advanced in place; record_out (fp64 [6 + 2A]) receives [episodes, sum_len,
+    sum_len2, wins0, wins1, draws, sum_G[A], sum_G2[A]] over the episodes that
+    ended in these T steps.  side_mask: the agents of side 0 (0 or all: no
+    sides, no wins).  scratch: float64 device tensor of
+    mas_episode_stats_scratch_doubles(N, A) (allocated here when None)."""
+    check(_episode_stats_call('episode_stats', rewards, dones, n_agents, ret_carry, len_carry, record_out, side_mask,
+                              stream, scratch))
+
+
+def episode_stats_reference(rewards, dones, n_agents, ret_carry, len_carry, side_mask=0):
+    """Plain torch restatement of mas_episode_stats with its order of
+    operations per env (the CPU trainer's, and the fallback for more agents
+    than the kernel takes): returns (the new ret_carry fp64 [N*A], the new
+    len_carry int32 [N], the record fp64 [6 + 2A]).  The carries given are not
+    written.  Across envs the terms are added in torch's order, not the
+    kernel's: the integer entries agree exactly, the fp64 sums within rounding."""
+    A = int(n_agents)
+    mask = _episode_side_mask(side_mask, A)
+    T = rewards.shape[0]
+    r = rewards.reshape(T, -1, A)
+    E, dev = r.shape[1], r.device
+    d = dones.reshape(T, E) != 0
+    G = ret_carry.reshape(E, A).to(torch.float64).clone()
+    ln = len_carry.reshape(E).to(torch.int32).clone()
+    rec = torch.zeros((len(EPISODE_RECORD_HEAD) + 2 * A,), dtype=torch.float64, device=dev)
+    sides = mask != 0 and mask != (1 << A) - 1
+    zG, zl, zE = torch.zeros_like(G), torch.zeros_like(ln), torch.zeros((E,), dtype=torch.float64, device=dev)
+    for t in range(T):
+        G = G + r[t].to(torch.float64)
+        ln = ln + 1
+        dt = d[t]
+        L = ln.to(torch.float64)
+        rec[0] += dt.sum()
+        rec[1] += torch.where(dt, L, zE).sum()
+        rec[2] += torch.where(dt, L * L, zE).sum()
+        Gd = torch.where(dt[:, None], G, zG)
+        rec[6:6 + A] += Gd.sum(0)
+        rec[6 + A:] += (Gd * Gd).sum(0)
+        if sides:
+            s0, s1 = zE, zE
+            for a in range(A):
+                if (mask >> a) & 1:
+                    s0 = s0 + G[:, a]
+                else:
+                    s1 = s1 + G[:, a]
+            rec[3] += (dt & (s0 > s1)).sum()
+            rec[4] += (dt & (s1 > s0)).sum()
+            rec[5] += (dt & (s0 == s1)).sum()
+        G = torch.where(dt[:, None], zG, G)
+        ln = torch.where(dt, zl, ln)
+    return G.reshape(-1), ln, rec
+
+
+class EpisodeStats:
+    """What the rollouts' finished episodes looked like (RecordEpisodeStatistics,
+    batched per rollout): the per-env carries of every agent's undiscounted
+    return (fp64 ``ret_carry`` [N*A]) and of the episode length (int32
+    ``len_carry`` [N]) across rollouts, ``last`` (the record of the latest
+    rollout, include/masurvival.h mas_episode_stats) and ``total`` (the sum of
+    all records), fp64 on `device`.  On a GPU ``update`` is mas_episode_stats;
+    elsewhere, and for a shape the kernel does not take (more agents per env
+    than episode_stats_geometry() reports: mas_episode_stats_scratch_doubles is
+    -1), the torch restatement.  Nothing is copied to the host before
+    ``summary``."""
+
+    def __init__(self, n_envs, n_agents, device, side_mask=0):
+        self.n_envs, self.n_agents, self.device = int(n_envs), int(n_agents), torch.device(device)
+        if self.n_envs < 1 or self.n_agents < 1:
+            raise ValueError(f'EpisodeStats: need n_envs and n_agents >= 1, got {n_envs} and {n_agents}')
+        self.side_mask = _episode_side_mask(side_mask, self.n_agents)
+        n = len(EPISODE_RECORD_HEAD) + 2 * self.n_agents
+        self.ret_carry = torch.zeros((self.n_envs * self.n_agents,), dtype=torch.float64, device=self.device)
+        self.len_carry = torch.zeros((self.n_envs,), dtype=torch.int32, device=self.device)
+        self.last = torch.zeros((n,), dtype=torch.float64, device=self.device)
+        self.total = torch.zeros_like(self.last)
+        self._scratch = None
+        self.lib = None
+        if self.device.type == 'cuda':
+            self.lib = load_library()
+            if not hasattr(self.lib, 'mas_episode_stats'):
+                raise MasError('the loaded library has no mas_episode_stats')
+            need = int(self.lib.mas_episode_stats_scratch_doubles(self.n_envs, self.n_agents))
+            if need >= 0:
+                self._scratch = torch.empty((need,), dtype=torch.float64, device=self.device)
+
+    @torch.no_grad()
+    def update(self, rewards, dones, group=None, reduce=None):
+        """Walk one rollout (rewards fp32 [T, N, A], dones uint8 [T, N], only
+        read): the carries advance, ``last`` becomes the rollout's record and
+        is added to ``total``.  reduce (default: whether a group is given):
+        all-reduce ``last`` over `group` first, so every rank ends with the
+        same record (the carries stay per rank)."""
+        if (rewards.dim() < 2 or rewards[0].numel() != self.n_envs * self.n_agents
+                or rewards.device.type != self.device.type):
+            raise ValueError(f'EpisodeStats.update: need rewards of {self.n_envs} x {self.n_agents} columns on '
+                             f'{self.device}, got {tuple(rewards.shape)} on {rewards.device}')
+        rc = MAS_ERR_UNSUPPORTED
+        if self._scratch is not None:
+            rc = _episode_stats_call('EpisodeStats.update', rewards, dones, self.n_agents, self.ret_carry,
+                                     self.len_carry, self.last, self.side_mask, None, self._scratch)
+        if rc == MAS_ERR_UNSUPPORTED:  # no GPU, no kernel for this shape, or refused with nothing launched
+            G, ln, rec = episode_stats_reference(rewards, dones, self.n_agents, self.ret_carry, self.len_carry,
+                                                 self.side_mask)
+            self.ret_carry.copy_(G)
+            self.len_carry.copy_(ln)
+            self.last.copy_(rec)
+        else:
+            check(rc)
+        if group is not None if reduce is None else reduce:
+            dist.all_reduce(self.last, group=group)
+        self.total += self.last
+
+    def summary(self, which='last'):
+        """Plain numbers from ``last`` or ``total`` (the one host copy):
+        episodes, mean_length, std_length, return and return_std (a list per
+        agent slot), wins (per side), draws, win_rate (side 0's).  Means are
+        over the finished episodes; all 0 when none finished."""
+        if which not in ('last', 'total'):
+            raise ValueError(f"EpisodeStats.summary: which must be 'last' or 'total', got {which!r}")
+        rec = getattr(self, which).tolist()
+        A, n = self.n_agents, rec[0]
+        k = 1.0 / n if n > 0 else 0.0
+        mean_len = rec[1] * k
+        ret = [g * k for g in rec[6:6 + A]]
+        return {'episodes': int(n), 'mean_length': mean_len,
+                'std_length': max(rec[2] * k - mean_len * mean_len, 0.0) ** 0.5,
+                'return': ret,
+                'return_std': [max(g2 * k - m * m, 0.0) ** 0.5 for g2, m in zip(rec[6 + A:], ret)],
+                'wins': [int(rec[3]), int(rec[4])], 'draws': int(rec[5]), 'win_rate': rec[3] * k}
+
+    def state_dict(self):
+        return {'ret_carry': self.ret_carry.detach().clone(), 'len_carry': self.len_carry.detach().clone(),
+                'last': self.last.detach().clone(), 'total': self.total.detach().clone(),
+                'n_agents': int(self.n_agents), 'side_mask': int(self.side_mask)}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        have = (int(sd['n_agents']), tuple(sd['ret_carry'].shape), tuple(sd['len_carry'].shape),
+                tuple(sd['last'].shape), tuple(sd['total'].shape), int(sd['side_mask']))
+        want = (self.n_agents, tuple(self.ret_carry.shape), tuple(self.len_carry.shape), tuple(self.last.shape),
+                tuple(self.total.shape), self.side_mask)
+        if have != want:
+            raise ValueError(f'EpisodeStats: checkpoint (n_agents, carry, length, record and total shapes, side_mask) '
+                             f'{have}, expected {want}')
+        self.ret_carry.copy_(sd['ret_carry'])
+        self.len_carry.copy_(sd['len_carry'])
+        self.last.copy_(sd['last'])
+        self.total.copy_(sd['total'])
+
+    @classmethod
+    def from_state_dict(cls, sd, device):
+        es = cls(sd['len_carry'].numel(), sd['n_agents'], device, sd['side_mask'])
+        es.load_state_dict(sd)
+        return es
 
 
 def gae_reference(rewards, values, dones, gamma, lam, n_agents):
@@ -1351,6 +1586,12 @@ class PPOTrainer:
             if not (cfg.reward_clip > 0):
                 raise ValueError(f'PPOConfig.reward_clip must be positive (inf: no clipping), got {cfg.reward_clip}')
             self.ret_norm = RetNorm(self._gae_columns(), self.device, cfg.reward_norm_eps)
+        # the episode statistics (EpisodeStats) over the whole buffer, every agent's columns under
+        # self-play too; also made by load_state_dict from a checkpoint that has them.
+        # cfg.episode_stats only decides whether they keep updating
+        self.ep_stats = None
+        if cfg.episode_stats:
+            self.ep_stats = EpisodeStats(env.n_envs, env.n_agents, self.device, self._side0_mask())
         fused = cfg.fused
         if fused is None:
             fused = self.device.type == 'cuda' and cfg.hidden == 256
@@ -1391,6 +1632,26 @@ class PPOTrainer:
         """Agent columns of the buffer GAE reads: every agent's, with self-play the learner's."""
         A = self.env.n_agents if self.learner_agents is None else len(self.learner_agents)
         return int(self.env.n_envs) * int(A)
+
+    def _side0_mask(self):
+        """Side 0 of the episode statistics: the learner's agents against an
+        opponent, otherwise agents range(A // 2) (Match's side 0; none for one agent)."""
+        A = int(self.env.n_agents)
+        side0 = self.learner_agents if self.opponent is not None else range(A // 2)
+        return _agent_mask(side0, A, 'side 0') if len(side0) else 0
+
+    def _episode_last_stats(self):
+        """last_stats' share of the latest rollout's record: device tensors, means over max(episodes, 1)."""
+        rec, A = self.ep_stats.last, self.ep_stats.n_agents
+        n = rec[0].clamp_min(1.0)
+        return {'episodes': rec[0].clone(), 'ep_length': rec[1] / n, 'ep_return': rec[6:6 + A] / n,
+                'win_rate': rec[3] / n}
+
+    def episode_summary(self, which='total'):
+        """EpisodeStats.summary of the training rollouts' episodes (plain numbers; a host copy)."""
+        if self.ep_stats is None:
+            raise ValueError('episode_summary: this trainer keeps no episode statistics (PPOConfig.episode_stats)')
+        return self.ep_stats.summary(which)
 
     def _attach_obs_norm(self, on):
         self.obs_norm = on
@@ -1656,6 +1917,9 @@ class PPOTrainer:
         else:
             _, v = self._fwd(b.obs[c.horizon])
             b.values[c.horizon].copy_(v)
+        if self.ep_stats is not None and c.episode_stats:
+            # every agent's rewards of the whole buffer, before the learner's rows are selected
+            self.ep_stats.update(b.rewards, b.dones, group=self.group, reduce=self.collectives)
         if b.learner is not None:
             # self-play: GAE, the statistics and the update see the learner's rows alone
             self._select_learner_rows()
@@ -1739,6 +2003,8 @@ class PPOTrainer:
             self.last_stats['active'] = share
         if c.reward_norm:
             self.last_stats['reward_scale'] = self.ret_norm.scale[0].clone()
+        if c.episode_stats:
+            self.last_stats.update(self._episode_last_stats())
         if c.obs_norm:
             self._obs_norm_after_update()
             self.fused.pack()
@@ -1781,6 +2047,8 @@ class PPOTrainer:
             self.last_stats['active'] = share[0]
         if c.reward_norm:
             self.last_stats['reward_scale'] = self.ret_norm.scale[0].clone()
+        if c.episode_stats:
+            self.last_stats.update(self._episode_last_stats())
         if c.obs_norm:
             self._obs_norm_after_update()
         self._sync_rollout_policy()
@@ -1804,6 +2072,8 @@ class PPOTrainer:
             sd['obs_norm'] = self.obs_norm.state_dict()  # three fp64 tensors and eps (match.load_policy reads it)
         if self.ret_norm is not None:
             sd['ret_norm'] = self.ret_norm.state_dict()  # count, mean, m2 (fp64), eps and the columns' carry
+        if self.ep_stats is not None:
+            sd['ep_stats'] = self.ep_stats.state_dict()  # the carries, the last record and the lifetime total
         if self.learner_agents is not None:
             # self-play: 'policy' stays the learner (match.load_policy reads it as any checkpoint's)
             sd['learner_agents'] = [int(a) for a in self.learner_agents]
@@ -1849,6 +2119,13 @@ class PPOTrainer:
             if self.ret_norm is None:
                 self.ret_norm = RetNorm(self._gae_columns(), self.device, self.cfg.reward_norm_eps)
             self.ret_norm.load_state_dict(sd['ret_norm'])
+        if 'ep_stats' in sd:
+            # restored whatever cfg.episode_stats says; a checkpoint without them leaves a flagged
+            # trainer's fresh statistics as they are
+            if self.ep_stats is None:
+                self.ep_stats = EpisodeStats(self.env.n_envs, self.env.n_agents, self.device,
+                                             self._side0_mask())
+            self.ep_stats.load_state_dict(sd['ep_stats'])
         self.opt.load_state_dict(sd['opt'])
         if self.fused_opt is not None:
             self.fused_opt.bind_state()

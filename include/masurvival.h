@@ -246,6 +246,53 @@ int mas_gae_scaled(int32_t T, int64_t n_columns, int32_t n_agents, const float* 
                    const float* values, const uint8_t* done, float gamma, float lam,
                    const float* reward_scale /* DEVICE float[1] */, float reward_clip,
                    float* advantages, float* returns, double* adv_sums, double* scratch, void* stream);
+/* Episode statistics of a rollout (additions within ABI version 3): the
+ * episodes the rollout finished, their lengths, every agent slot's
+ * undiscounted return and which side won.  All pointers are DEVICE pointers;
+ * the call is stream-ordered, allocates nothing, does not synchronise and can
+ * be captured.  rewards and done are only read.
+ *
+ * Per env e, steps t = 0..T-1 in order, agents a ascending, from the carries
+ * G[a] = ret_carry[e * n_agents + a] (fp64) and len = len_carry[e] (both
+ * in/out: they persist across rollouts, 0 at the start):
+ *   G[a] += (double)rewards[t][e][a]      one fp64 add per step
+ *   len  += 1
+ *   if done[t][e] != 0:                    (any nonzero byte)
+ *       episodes += 1;  sum_len += len;  sum_len2 += len * len
+ *       sum_G[a] += G[a];  sum_G2[a] += G[a] * G[a]     each product rounded once
+ *       s0 = the sum of G[a] over the agents in side_mask, a ascending, from
+ *            +0.0;  s1 = the same over the other agents
+ *       wins0 += s0 > s1;  wins1 += s1 > s0;  draws += s0 == s1
+ *       G[:] = 0;  len = 0
+ * The step that ends an episode counts towards it: the rewards of step t
+ * belong to the episode that done[t] closes.  A NaN side sum is none of win,
+ * loss or draw.  len * len is formed in fp64.
+ *
+ *   record = [episodes, sum_len, sum_len2, wins0, wins1, draws,
+ *             sum_G[0..n_agents), sum_G2[0..n_agents)]
+ * double[6 + 2 * n_agents], the totals over all envs of this call (written,
+ * not added to).  With side_mask 0 or all agents there are no two sides and
+ * entries 3..5 are 0.  The integer entries (0..5) are exact while below 2^53.
+ * The envs' terms are added in a fixed order that is not the envs' order.
+ *
+ * scratch: double[mas_episode_stats_scratch_doubles(n_envs, n_agents)] (-1 for
+ * n_envs < 1, n_agents outside 1..8, the agent counts the call takes, or a
+ * grid that does not fit), the call's per-workgroup partial sums: the same
+ * inputs give the same bits, whatever scratch held.
+ *
+ * MAS_ERR_INVALID_ARG before any HIP call, the shape first and then the
+ * pointers: T <= 0, n_envs <= 0, n_agents < 1, a side_mask bit at or above
+ * n_agents, a null pointer, n_envs too large for the grid.  After those,
+ * n_agents > 8 (the capacity classes' limit: an env's returns live in
+ * registers) is MAS_ERR_UNSUPPORTED with nothing launched. */
+int64_t mas_episode_stats_scratch_doubles(int64_t n_envs, int32_t n_agents);
+int mas_episode_stats(int32_t T, int64_t n_envs, int32_t n_agents, uint32_t side_mask,
+                      const float* rewards,  /* [T][n_envs * n_agents] */
+                      const uint8_t* done,   /* [T][n_envs], any nonzero byte is done */
+                      double* ret_carry,     /* [n_envs * n_agents] in/out */
+                      int32_t* len_carry,    /* [n_envs] in/out */
+                      double* record,        /* [6 + 2 * n_agents], written, not added to */
+                      double* scratch, void* stream);
 /* mas_adv_normalize: the n advantages (DEVICE float, 16-B aligned)
  * normalised in place from stats = DEVICE double[3] (sum, sum of squares,
  * count: mas_gae's adv_sums and the count, summed over ranks):
