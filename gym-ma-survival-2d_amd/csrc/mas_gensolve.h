@@ -593,13 +593,15 @@ __device__ __forceinline__ void island_solve_one(const Params& P, const SolveRec
 
 // One world step's Collide + Solve of env e on this lane's group (lane s of
 // the group).  valid: the group holds an env (every lane of the wave runs the
-// ballots and the barrier).  rec: this workgroup's contact records.
+// ballots and the barrier).  rec: this workgroup's contact records;
+// toi_snap: its groups' TOI event snapshots ([kToiSnapW][env of the wave]).
 // b2World::SolveTOI of the step runs on the group too (toi_agent_group,
 // mas_physics.h: lane s owns static s), its agent loop by rank (each group's
 // k-th TOI agent in round k).
 template <class C>
 __device__ __forceinline__ void gen_solve_group(const Params& P, uint32_t* __restrict__ state, int64_t N, int64_t e,
-                                                bool valid, int s, float* rec_lds, int slot, int pf = 0)
+                                                bool valid, int s, float* rec_lds, uint32_t* toi_snap, int slot,
+                                                int pf = 0)
 {
     using SS = SolveShape<C>;
     using TW = StateWords<C>;
@@ -1105,7 +1107,8 @@ __device__ __forceinline__ void gen_solve_group(const Params& P, uint32_t* __res
             L.bmeta[k2] = bmeta;
         }
         const uint32_t asti = sel(ast, i);
-        const ToiGroupOut o = toi_agent_group<C, G>(L, P, K, i, s, sel(cs, i), sel(as_, i), asti, dt);
+        const ToiGroupOut o = toi_agent_group<C, G>(L, P, K, i, s, sel(cs, i), sel(as_, i), asti, dt,
+                                                      toi_snap + slot, SS::EPW);
         toi_events += o.events;
         put(c, i, o.c);
         put(a, i, o.a);

@@ -193,6 +193,7 @@ MAS_KERNEL_OCC(kSolveOcc<C>) void k_gen_solve_g(Params P, uint32_t* __restrict__
 {
     using SS = SolveShape<C>;
     __shared__ float rec[kRecW * SS::KL * SS::EPW];
+    __shared__ uint32_t toi_snap[kToiSnapW * SS::EPW];  // the previous TOI event per group (toi_agent_group)
     const int slot = (int)threadIdx.x / SS::G, s = (int)threadIdx.x % SS::G;
     // (the main list in XCD-aware runs of 16 waves: a shard's entries, one
     // contiguous env range of k_pre, mostly on one XCD)
@@ -206,11 +207,11 @@ MAS_KERNEL_OCC(kSolveOcc<C>) void k_gen_solve_g(Params P, uint32_t* __restrict__
     // ws = -1: both world steps in this launch.  The second reloads what the
     // first stored, by other lanes of this wave: a workgroup-scope fence (the
     // wave is the workgroup) orders those stores before its loads
-    gen_solve_group<C>(P, state, N, e, valid, s, rec, slot, 0);
+    gen_solve_group<C>(P, state, N, e, valid, s, rec, toi_snap, slot, 0);
     if (ws < 0) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         MAS_PROF(P, 7);  // the fence's wait for the first world step's stores
-        gen_solve_group<C>(P, state, N, e, valid, s, rec, slot, 8);
+        gen_solve_group<C>(P, state, N, e, valid, s, rec, toi_snap, slot, 8);
     }
     MAS_PROF_FLUSH(P, P.gen_sparse ? 4 : 0, 0);
 }

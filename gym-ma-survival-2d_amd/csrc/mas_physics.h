@@ -718,6 +718,11 @@ MAS_HD V2 static_pos(const EnvL<C>& L, const Params& P, int q)
     return q < kNumWalls ? P.wall_pos[q] : L.bp[q - kNumWalls];
 }
 
+// Words of the previous TOI event's state that a group keeps in LDS
+// (toi_agent_group's repeated-event test): the sweep (7), v, w (3), the
+// group's touching and enabled ballots, the min static.
+enum { kToiSnapW = 13 };
+
 struct ToiGroupOut {
     V2 c, v;
     float a, w;
@@ -729,6 +734,7 @@ struct ToiGroupOut {
 // agent's sweep start (b2Sweep c0/a0 of this world step); L: the env after
 // the island solve; K: the contact memory in HBM (impulse resets of this
 // lane's contact are written there); t0: agent I's touching word.
+// snap: this group's kToiSnapW snapshot words in LDS, `stride` words apart.
 // test builds: 1 sends every TOI island through the general (more contacts
 // than compact slots) branch, so the parity tests cover it
 #ifndef MAS_TOI_FORCE_FALLBACK
@@ -736,7 +742,8 @@ struct ToiGroupOut {
 #endif
 template <class C, int G, class KT>
 __device__ __forceinline__ ToiGroupOut toi_agent_group(const EnvL<C>& L, const Params& P, const KT& K, int I, int s,
-                                                       V2 c0, float a0, uint32_t t0, float dt)
+                                                       V2 c0, float a0, uint32_t t0, float dt, uint32_t* snap,
+                                                       int stride)
 {
     static_assert(G >= C::NS && G <= 64 && (G & (G - 1)) == 0, "one lane per static");
     const float r = P.agent_r, m = P.inv_mass, Ii = P.inv_I;
@@ -760,6 +767,8 @@ __device__ __forceinline__ ToiGroupOut toi_agent_group(const EnvL<C>& L, const P
     const int lane = (int)(threadIdx.x & 63);
     const int base = lane & ~(G - 1);
     const uint64_t gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << base;
+    // no previous event yet (no static has this index)
+    if (s == 0) snap[(kToiSnapW - 1) * stride] = ~0u;
     for (int guard = 0; guard < 9 * C::NS + 1; ++guard) {
         // (1) this lane's stale TOI: conservative pre-test, else b2TimeOfImpact
         if (mine && en && cnt <= 8 && !val) {
@@ -813,6 +822,9 @@ __device__ __forceinline__ ToiGroupOut toi_agent_group(const EnvL<C>& L, const P
         if (!gshfl<G>(tch, minS)) {
             if (s == minS) en = false;
             sw = backup;
+            // (a restored non-event counted on its lane: the next event is
+            // not compared across it)
+            if (s == 0) snap[(kToiSnapW - 1) * stride] = ~0u;
             continue;
         }
         ++events;
@@ -956,6 +968,42 @@ __device__ __forceinline__ ToiGroupOut toi_agent_group(const EnvL<C>& L, const P
         sw.c = cB;
         sw.a = aB;
         val = false;
+        // (6) a repeated event.  The next iteration is a function of the
+        // sweep, v, w, every lane's touch and en (val is false on every lane)
+        // and of the counters through `cnt <= 8` alone.  If this event left
+        // all of that, bit for bit, as the previous event of this call had
+        // left it (no restored non-event between them, the same min static),
+        // the iteration that follows sees what this one saw: the same TOIs,
+        // the same min static (ties: the lowest index), the same contact
+        // updates and Gauss-Seidel sweeps, the same state again -- until the
+        // min contact's counter passes b2_maxSubSteps.  Those n = 9 - cnt
+        // further events are counted here without being computed.  Their
+        // impulse resets (K.set_asni / K.set_asti of zeros, from the same
+        // touch and the same collide_pc result) write what this event's
+        // already wrote.  The snapshot lives in LDS, not in registers: the
+        // kernel has none to spare.
+        {
+            const uint32_t tb = (uint32_t)((__ballot(mine && touch) & gmask) >> base);
+            const uint32_t eb = (uint32_t)((__ballot(mine && en) & gmask) >> base);
+            const uint32_t now[kToiSnapW] = {__float_as_uint(sw.c0.x), __float_as_uint(sw.c0.y), __float_as_uint(sw.a0),
+                                             __float_as_uint(sw.c.x),  __float_as_uint(sw.c.y),  __float_as_uint(sw.a),
+                                             __float_as_uint(sw.alpha0), __float_as_uint(vB.x),  __float_as_uint(vB.y),
+                                             __float_as_uint(wB),      tb,                       eb,
+                                             (uint32_t)minS};
+            wave_lds_sync();  // lane 0's earlier snapshot stores
+            uint32_t diff = 0u;
+#pragma unroll
+            for (int j = 0; j < kToiSnapW; ++j) diff |= snap[j * stride] ^ now[j];
+            wave_lds_sync();  // every lane has read the previous snapshot
+            if (diff == 0u) {
+                const int n = gshfl<G>(9 - cnt, minS);  // selections `cnt <= 8` still allows
+                events += n;
+                if (s == minS) cnt = 9;
+            } else if (s == 0) {
+#pragma unroll
+                for (int j = 0; j < kToiSnapW; ++j) snap[j * stride] = now[j];
+            }
+        }
     }
     ToiGroupOut o;
     o.c = sw.c;
