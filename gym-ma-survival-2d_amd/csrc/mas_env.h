@@ -124,6 +124,24 @@ struct Params {
     int64_t x_ld;
 };
 
+// Params is every env kernel's first by-value argument, so it sits at the
+// start of the kernarg segment.  A kernel that reads it through KernParams
+// can reread() it at a phase boundary: the fields the next phase uses are
+// then loaded again (scalar loads) instead of being held in SGPRs from the
+// kernel's start, where the compiler hoists every load of an invariant
+// argument.  Held across a whole kernel they spilled into VGPR lanes, and
+// those VGPRs in turn into scratch (k_post_lanes, 2v2: 265 SGPR and 10 VGPR
+// spills, 36 B of scratch per lane -> 2, 0 and 0 with a reread per phase).
+struct KernParams {
+    const __attribute__((address_space(4))) char* p;
+    __device__ __forceinline__ static KernParams get()
+    {
+        return {(const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr()};
+    }
+    __device__ __forceinline__ void reread() { asm volatile("" : "+s"(p)); }
+    __device__ __forceinline__ const Params& operator*() const { return *(const Params*)p; }
+};
+
 constexpr int kListShards = 64;   // shards of the general-path list (Params::list_shards)
 constexpr int kShardStride = 64;  // ints between two shard counters (256 B: their own lines)
 constexpr int kListSlack = kListShards * 64;  // list entries allocated past N (the shards' rounding)

@@ -188,6 +188,13 @@ __device__ __forceinline__ ListPos list_pos(const Params& P, int64_t N, int64_t 
 // mas_gensolve.h).  Waves per SIMD (the register budget): 2.
 template <class C>
 constexpr int kSolveOcc = 2;
+// Both world steps through one copy of the world step's code (a rolled loop)
+// in the classes with up to 4 agent slots: half the kernel's code (2v2:
+// 234 KB -> 111 KB), fewer SGPR spills (229 -> 109) and no scratch.  The 8-slot
+// classes (xl, xxl), which spill either way, take more scratch in the loop
+// form (232 -> 236 and 200 -> 228 B per lane) and keep the two inlined copies.
+template <class C>
+constexpr bool kSolveRolled = C::AM <= 4;
 template <class C>
 MAS_KERNEL_OCC(kSolveOcc<C>) void k_gen_solve_g(Params P, uint32_t* __restrict__ state, int64_t N, int ws)
 {
@@ -203,15 +210,35 @@ MAS_KERNEL_OCC(kSolveOcc<C>) void k_gen_solve_g(Params P, uint32_t* __restrict__
     if (!lp.any) return;  // the whole workgroup (one wave)
     MAS_PROF(P, -1);
     const bool valid = lp.valid;
-    const int64_t e = lp.e;
     // ws = -1: both world steps in this launch.  The second reloads what the
     // first stored, by other lanes of this wave: a workgroup-scope fence (the
     // wave is the workgroup) orders those stores before its loads
-    gen_solve_group<C>(P, state, N, e, valid, s, rec, toi_snap, slot, 0);
-    if (ws < 0) {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        MAS_PROF(P, 7);  // the fence's wait for the first world step's stores
-        gen_solve_group<C>(P, state, N, e, valid, s, rec, toi_snap, slot, 8);
+    if constexpr (kSolveRolled<C>) {
+        // Every iteration takes the kernel arguments, the state base and the
+        // env index from behind an opaque point: what the body derives from
+        // them (the Params fields, the env's state addresses) would otherwise
+        // be hoisted out of the loop and held in registers across the whole
+        // world step, which spilled (2v2: 576 B of scratch per lane).
+        const int nws = ws < 0 ? 2 : 1;
+#pragma nounroll
+        for (int k = 0; k < nws; ++k) {
+            if (k) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                MAS_PROF(P, 7);  // the fence's wait for the first world step's stores
+            }
+            KernParams kpar = KernParams::get();
+            kpar.reread();
+            const int64_t e = (int64_t)opq((uint64_t)lp.e);
+            gen_solve_group<C>(*kpar, opq_s(state), opq_s(N), e, valid, s, rec, toi_snap, slot, 8 * k);  // (phases 0.. / 8..)
+        }
+    } else {
+        const int64_t e = lp.e;
+        gen_solve_group<C>(P, state, N, e, valid, s, rec, toi_snap, slot, 0);
+        if (ws < 0) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            MAS_PROF(P, 7);  // the fence's wait for the first world step's stores
+            gen_solve_group<C>(P, state, N, e, valid, s, rec, toi_snap, slot, 8);
+        }
     }
     MAS_PROF_FLUSH(P, P.gen_sparse ? 4 : 0, 0);
 }

@@ -879,8 +879,21 @@ inline bool reset_fits_post(const Params& P)
 #else
 #define MAS_POST_BOUNDS __launch_bounds__(kWG, MAS_POST_OCC)
 #endif
+// The kernel reads its arguments from the kernarg segment and rereads them at
+// every phase boundary (KernParams, mas_env.h): SGPR spills 195-460 -> 2-34
+// and no scratch in every class (xl: 88-116 B per lane before).  Not in the
+// xxl class, whose kernel went from 255-256 to 268-270 VGPRs with it, one wave
+// per SIMD instead of two: it keeps the by-value argument.
+template <class C>
+constexpr bool kPostReread = !(C::AM == 8 && C::BM > 8);
+template <class C>
+__device__ __forceinline__ const Params& post_params(const KernParams& k, const Params& by_value)
+{
+    if constexpr (kPostReread<C>) return *k;
+    else return by_value;
+}
 template <class C, int M>
-__global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ state, int64_t N,
+__global__ MAS_POST_BOUNDS void k_post_lanes(Params P_, uint32_t* __restrict__ state, int64_t N,
                                                        float* __restrict__ obs, float* __restrict__ rew,
                                                        uint8_t* __restrict__ done, int ar)
 {
@@ -890,6 +903,10 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
     static_assert(kWG % AM == 0 && (AM & (AM - 1)) == 0, "agent lane groups must tile a wave");
     static_assert(C::NB <= 64 && AM <= 8, "16-bit camera list entries, 64-bit body masks");
     __shared__ PostLds<C> lds;
+    // (P: the arguments as last reread from the kernarg segment, once per
+    // phase -- KernParams, mas_env.h)
+    KernParams kpar = KernParams::get();
+#define P post_params<C>(kpar, P_)
     MAS_PROF(P, -1);
     retire_phys_count<M>(P);
     const int lane = (int)threadIdx.x;
@@ -974,6 +991,7 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
     V.ag(5, i) = g.w;
     wave_lds_sync();  // the wave's LDS groups are loaded (one-wave block)
     MAS_PROF(P, 41);
+    if (kPostReread<C>) kpar.reread();
     // ---- boxes: Health.post_step + despawn (the first post_step hook, dict
     // order: the boxes group before the agents)
     bool bchanged = false;
@@ -997,6 +1015,7 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
     // ---- Cameras.post_step (simulation.py:314-354): camera i of slot j
     cameras_v<C>(lds, V, P, true, valid && alive, alive_m, g.c, g.a, i, j, lane);
     MAS_PROF(P, 42);
+    if (kPostReread<C>) kpar.reread();
     // ---------------- agents post_step (step_post, mas_step.h) ----------------
     uint32_t dirty = kGZone | kGStat;
     // Health.post_step -> despawn dead (id order): TrackDeaths, IndexBodies,
@@ -1276,6 +1295,7 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
         }
     }
     MAS_PROF(P, 43);
+    if (kPostReread<C>) kpar.reread();
     // the auto-reset in place (reset_in_post): a done env's post-step groups
     // are not stored, its reset state is (below)
     const bool rs = ar && P.reset_in_post && valid && is_done;
@@ -1429,6 +1449,7 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
         }
     }
     MAS_PROF(P, 44);
+    if (kPostReread<C>) kpar.reread();
     // ---------------- fetch_observations: rows from LDS ----------------
     V.ag(6, i) = (float)g.health;
     int lastmeta = 0;
@@ -1473,6 +1494,7 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P, uint32_t* __restrict__ st
     }
     MAS_PROF(P, 45);
     MAS_PROF_FLUSH(P, M == kGenEnvs ? 5 : 2, 41);
+#undef P
 }
 
 }  // namespace mas
