@@ -382,8 +382,14 @@ __device__ __forceinline__ bool world_step_fast_lane(AgentL<C>& g, bool alive, b
         }
     }
     // SolveTOI: the sweep of an awake agent must be rejected by the cheap
-    // test (the same world-AABB pre-filter as world_step_fast)
+    // test (the same world-AABB pre-filter as world_step_fast).  The cull
+    // only chooses the statics that toi_reject then tests; its box must hold
+    // toi_reject's grown rectangle, and a larger one costs a few exact tests
+    // and changes no result.  It keeps the 0.02 toi_reject had before
+    // kToiRejectMargin (>= it, so still a superset) with 0.05 of slack on
+    // top: deliberately not tied to the exact test's margin.
     if (alive && awake) {
+        static_assert(kToiRejectMargin <= 0.02f, "the cull's box holds toi_reject's rectangle");
         const float Rp =
             1.4143f * ((kPolyRadius + P.agent_r - 3.0f * kLinearSlop) + 0.25f * kLinearSlop + 0.02f) + 0.05f;
         const V2 slo = mk(fminf(c0.x, g.c.x) - Rp, fminf(c0.y, g.c.y) - Rp);

@@ -604,13 +604,56 @@ MAS_HD int time_of_impact(const ToiPoly& T, const Sweep& B, float rB, float& tou
 }
 
 // Conservative pre-test (device only, changes no result): the sweep segment
-// against the polygon core's local rectangle grown by target + tolerance +
-// margin.  b2TimeOfImpact reports "touching" only where the core-to-point
-// distance drops below target + tolerance, so a segment that misses the
-// grown rectangle always yields alpha = 1.
+// against the polygon core's local rectangle [-ex, ex] x [-ey, ey] grown by
+// thr + kToiRejectMargin, thr = target + tolerance.  A rejected segment keeps
+// the gauge g(x) = max(|lx| - ex, |ly| - ey) above thr + margin on the whole
+// sweep, and g(x) <= dist(x, core) because the core lies inside the rectangle.
+//
+// Why a rejected call cannot return "touching" (so alpha = 1 either way):
+// time_of_impact returns kToiTouching at two places only, both at a time t1
+// of the sweep (the point moves on the straight segment c0 -> c, the static
+// does not move), and at both the separation it tests is the core-to-point
+// distance at t1:
+//  (a) `distance < target + tolerance`: gjk's distance at t1 itself;
+//  (b) `s1 <= target + tolerance`: s1 = sep_eval(f, t1) with f = sep_init(cache,
+//      t1) built from the gjk call at this same t1 -- t1 changes only by
+//      `t1 = t2; break`, which leaves the push-back loop for a new gjk and a
+//      new f.  At its own t1 the points axis is (pB - closest vertex)
+//      normalised, and that vertex is the support along it (the static's
+//      support index never changes: the axis is fixed and the static rests),
+//      so s1 = |pB - vertex|; the face axis is the normal of the witness edge
+//      whose interior holds the closest point, so s1 = the distance to the
+//      edge's line = the distance to the core.
+// A face axis stays fixed while t moves, so at t > t1 its separation can be
+// small where the point has slid past the end of the face and is far from the
+// core.  That value only ends the root finder (`t1 = t2; break`, or the next
+// t2); the next pass computes gjk at the new t1 and takes (a) or builds a new
+// axis there.  It is never reported as touching.  So touching implies
+// dist(x(t1), core) <= thr up to rounding, hence g <= thr there: not rejected.
+//
+// Rounding, at arena coordinates |x| < 16 and sums < 32 (half an ulp 4.8e-7 /
+// 9.5e-7): here xmult is one subtraction and three operations per coordinate
+// (< 4e-6), the extents one addition (< 1e-6), the slab divisions two
+// roundings relative to t <= 1 times a sweep shorter than 1 (< 3e-7);
+// time_of_impact's side is sweep_point (three roundings, 1.5e-6), xmul of the
+// vertices (1.5e-6), gjk's barycentric witness points (3e-6) and the small
+// differences after them (< 1e-6).  Together below 2e-5; the margin is 100
+// times that.  |x| < 16 is what spawn_grid.floor_size <= 30 gives (walls at
+// +- floor_size / 2, every named config has 20).  The bound is a count of
+// half-ulps of the coordinates, so it doubles with each doubling of the
+// arena: 4e-5 up to floor_size 62, 1.6e-4 up to 250, where the margin is
+// still more than 10 times it; a larger floor_size needs a larger margin.
+// R below is time_of_impact's target + tolerance, its fmax included, so a
+// small agent radius is covered too.  (The 0.02 before it, four slops, let every resting or sliding
+// contact -- core distance about totalRadius - 0.005, above thr = totalRadius
+// - 0.01375 -- through to a full root-find that returned alpha = 1.)
+// scripts/toi_pretest_probe.py counts, on the oracle, what each margin keeps
+// and that no rejected call touched.
+constexpr float kToiRejectMargin = 0.002f;
 MAS_HD bool toi_reject(const StaticG& g, V2 p0, V2 p1, float rB)
 {
-    const float R = (kPolyRadius + rB - 3.0f * kLinearSlop) + 0.25f * kLinearSlop + 0.02f;
+    const float R =
+        fmax_b2(kLinearSlop, kPolyRadius + rB - 3.0f * kLinearSlop) + 0.25f * kLinearSlop + kToiRejectMargin;
     V2 l0 = xmult(g.p, g.q, p0), l1 = xmult(g.p, g.q, p1);
     float ex = 0.0f, ey = 0.0f;
     for (int k = 0; k < 4; ++k) {

@@ -670,18 +670,24 @@ __device__ __forceinline__ void cameras_v(PostLds<C>& lds, const PostV<C>& V, co
     if (cam_on) {
         p = __popc(alive_m & ((1u << i) - 1u));
         const Rot q = rot_of(ang);
-        const int nb = V.nbox(), ni = V.nbi(), nh = V.nheal();
+        // omniscient observations read `seen` for the other agents only
+        // (seen_mask, write_obs_row_seq), and nothing else reads it: boxes,
+        // items, heals and walls are no candidates then and their seen rows
+        // stay zero.  They still occlude: ray_cast_pv culls every body.
+        if (!P.omniscient) {
+            const int nb = V.nbox(), ni = V.nbi(), nh = V.nheal();
 #pragma unroll
-        for (int b = 0; b < C::BM; ++b) {
-            if (b < nb && poly_test_point(P.cone, pos, q, V.bp(b))) cand |= 1ull << (BIdx<C>::box + b);
-            if (b < ni && poly_test_point(P.cone, pos, q, V.ip(b))) cand |= 1ull << (BIdx<C>::bitem + b);
+            for (int b = 0; b < C::BM; ++b) {
+                if (b < nb && poly_test_point(P.cone, pos, q, V.bp(b))) cand |= 1ull << (BIdx<C>::box + b);
+                if (b < ni && poly_test_point(P.cone, pos, q, V.ip(b))) cand |= 1ull << (BIdx<C>::bitem + b);
+            }
+#pragma unroll
+            for (int h = 0; h < C::HM; ++h)
+                if (h < nh && poly_test_point(P.cone, pos, q, V.hp(h))) cand |= 1ull << (BIdx<C>::heal + h);
+#pragma unroll
+            for (int w = 0; w < kNumWalls; ++w)
+                if (poly_test_point(P.cone, pos, q, P.wall_pos[w])) cand |= 1ull << (BIdx<C>::wall + w);
         }
-#pragma unroll
-        for (int h = 0; h < C::HM; ++h)
-            if (h < nh && poly_test_point(P.cone, pos, q, V.hp(h))) cand |= 1ull << (BIdx<C>::heal + h);
-#pragma unroll
-        for (int w = 0; w < kNumWalls; ++w)
-            if (poly_test_point(P.cone, pos, q, P.wall_pos[w])) cand |= 1ull << (BIdx<C>::wall + w);
 #pragma unroll
         for (int k = 0; k < AM; ++k)
             if (k != i && bit(alive_m, k) && poly_test_point(P.cone, pos, q, V.agent(k)))

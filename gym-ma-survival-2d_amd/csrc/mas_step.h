@@ -346,18 +346,22 @@ __device__ __forceinline__ void update_seen(const EnvL<C>& L, const Params& P, S
         const V2 pos = L.c[i];
         const Rot q = rot_of(L.a[i]);
         const uint32_t tag = ((uint32_t)p << 11) | ((uint32_t)i << 8);
+        // omniscient observations read `seen` for the other agents only:
+        // the other bodies are no candidates then (cameras_v, mas_post_lanes.h)
+        if (!P.omniscient) {
 #pragma unroll
-        for (int b = 0; b < C::BM; ++b)
-            if (b < L.nbox && poly_test_point(P.cone, pos, q, L.bp[b])) scr.pr(np++) = tag | (BIdx<C>::box + b);
+            for (int b = 0; b < C::BM; ++b)
+                if (b < L.nbox && poly_test_point(P.cone, pos, q, L.bp[b])) scr.pr(np++) = tag | (BIdx<C>::box + b);
 #pragma unroll
-        for (int b = 0; b < C::BM; ++b)
-            if (b < L.nbi && poly_test_point(P.cone, pos, q, L.ip[b])) scr.pr(np++) = tag | (BIdx<C>::bitem + b);
+            for (int b = 0; b < C::BM; ++b)
+                if (b < L.nbi && poly_test_point(P.cone, pos, q, L.ip[b])) scr.pr(np++) = tag | (BIdx<C>::bitem + b);
 #pragma unroll
-        for (int h = 0; h < C::HM; ++h)
-            if (h < L.nheal && poly_test_point(P.cone, pos, q, L.hp[h])) scr.pr(np++) = tag | (BIdx<C>::heal + h);
+            for (int h = 0; h < C::HM; ++h)
+                if (h < L.nheal && poly_test_point(P.cone, pos, q, L.hp[h])) scr.pr(np++) = tag | (BIdx<C>::heal + h);
 #pragma unroll
-        for (int w = 0; w < kNumWalls; ++w)
-            if (poly_test_point(P.cone, pos, q, P.wall_pos[w])) scr.pr(np++) = tag | (BIdx<C>::wall + w);
+            for (int w = 0; w < kNumWalls; ++w)
+                if (poly_test_point(P.cone, pos, q, P.wall_pos[w])) scr.pr(np++) = tag | (BIdx<C>::wall + w);
+        }
 #pragma unroll
         for (int j = 0; j < C::AM; ++j)
             if (j != i && bit(L.alive_m, j) && poly_test_point(P.cone, pos, q, L.c[j]))
@@ -407,18 +411,20 @@ __device__ __forceinline__ void update_seen_dealt(const EnvL<C>& L, const Params
             if (!bit(L.alive_m, i)) continue;
             const V2 pos = L.c[i];
             const Rot q = rot_of(L.a[i]);
+            if (!P.omniscient) {  // as update_seen: agents only under omniscient observations
 #pragma unroll
-            for (int b = 0; b < C::BM; ++b)
-                if (b < L.nbox && poly_test_point(P.cone, pos, q, L.bp[b])) cand[i] |= 1ull << (BIdx<C>::box + b);
+                for (int b = 0; b < C::BM; ++b)
+                    if (b < L.nbox && poly_test_point(P.cone, pos, q, L.bp[b])) cand[i] |= 1ull << (BIdx<C>::box + b);
 #pragma unroll
-            for (int b = 0; b < C::BM; ++b)
-                if (b < L.nbi && poly_test_point(P.cone, pos, q, L.ip[b])) cand[i] |= 1ull << (BIdx<C>::bitem + b);
+                for (int b = 0; b < C::BM; ++b)
+                    if (b < L.nbi && poly_test_point(P.cone, pos, q, L.ip[b])) cand[i] |= 1ull << (BIdx<C>::bitem + b);
 #pragma unroll
-            for (int h = 0; h < C::HM; ++h)
-                if (h < L.nheal && poly_test_point(P.cone, pos, q, L.hp[h])) cand[i] |= 1ull << (BIdx<C>::heal + h);
+                for (int h = 0; h < C::HM; ++h)
+                    if (h < L.nheal && poly_test_point(P.cone, pos, q, L.hp[h])) cand[i] |= 1ull << (BIdx<C>::heal + h);
 #pragma unroll
-            for (int w = 0; w < kNumWalls; ++w)
-                if (poly_test_point(P.cone, pos, q, P.wall_pos[w])) cand[i] |= 1ull << (BIdx<C>::wall + w);
+                for (int w = 0; w < kNumWalls; ++w)
+                    if (poly_test_point(P.cone, pos, q, P.wall_pos[w])) cand[i] |= 1ull << (BIdx<C>::wall + w);
+            }
 #pragma unroll
             for (int j = 0; j < C::AM; ++j)
                 if (j != i && bit(L.alive_m, j) && poly_test_point(P.cone, pos, q, L.c[j]))
