@@ -65,6 +65,11 @@ hipError_t obs_norm_merge(int n_cols, double* state, const double* batch, double
 hipError_t policy_pack_norm(int D, const float* W1, const float* b1, const float* W2, const float* b2,
                             const float* W3, const float* b3, const float* mean, const float* inv_std, void* packed,
                             hipStream_t s);
+// scripted baseline opponents (mas_bot.hip)
+int64_t bot_act_blocks(int64_t n_rows);
+hipError_t bot_act(int kind, int64_t n_envs, int n_agents, uint32_t mask, int teams, int n_heals, int o_agent,
+                   int o_zone, int o_oth, int o_othm, int o_heal, int o_healm, int o_hsm, float use_below, float reach,
+                   const void* x, int64_t x_stride, int8_t* actions, hipStream_t s);
 // episode statistics of a rollout (mas_epstats.hip)
 int episode_stats_max_agents();
 int64_t episode_stats_blocks(int64_t n_envs);
@@ -573,37 +578,40 @@ struct mas_handle {
     int par;  // which of the two slow-list count slots the next mas_step appends to
 };
 
-static void build_layout(mas_handle* h)
+// The observation layout of a config: the pure part of build_layout, shared
+// with mas_bot_act, which has no handle.  off_of[] receives the first column
+// of each key in ObsKey order, -1 for a key the config does not have.
+enum ObsKey { kAgent, kBoxItems, kBoxItemsMask, kBoxSlot, kBoxSlotMask, kBoxes, kBoxesMask, kHealSlot, kHealSlotMask,
+              kHeals, kHealsMask, kLidars, kOthers, kOthersMask, kZone, kNumObsKeys };
+static void layout_of(const mas_config& c, mas_obs_layout& L, int off_of[kNumObsKeys])
 {
-    const mas_config& c = h->cfg;
     int A = c.n_agents, H = c.n_heals, B = c.n_boxes, as_ = 8 + (c.teams ? 1 : 0);
-    mas_obs_layout& L = h->layout;
     memset(&L, 0, sizeof(L));
     L.n_agents = A;
-    struct K { const char* name; int ndim, s0, s1; bool on; int* off; };
-    Params& P = h->P;
-    K keys[] = {
-        {"agent", 1, as_, 0, true, &P.o_agent},
-        {"box_items", 2, B, 10, B > 0, &P.o_bi},
-        {"box_items_mask", 1, B, 0, B > 0, &P.o_bim},
-        {"box_slot", 2, 1, 8, B > 0, &P.o_bs},
-        {"box_slot_mask", 1, 1, 0, B > 0, &P.o_bsm},
-        {"boxes", 2, B, 11, B > 0, &P.o_box},
-        {"boxes_mask", 1, B, 0, B > 0, &P.o_boxm},
-        {"heal_slot", 2, 1, 1, H > 0, &P.o_hs},
-        {"heal_slot_mask", 1, 1, 0, H > 0, &P.o_hsm},
-        {"heals", 2, H, 2, H > 0, &P.o_heal},
-        {"heals_mask", 1, H, 0, H > 0, &P.o_healm},
-        {"lidars", 1, c.lidar_n_lasers, 0, c.lidar_n_lasers > 0, &P.o_lid},
-        {"others", 2, A - 1, as_, true, &P.o_oth},
-        {"others_mask", 1, A - 1, 0, true, &P.o_othm},
-        {"zone", 1, 6, 0, true, &P.o_zone},
+    struct K { const char* name; int ndim, s0, s1; bool on; };
+    const K keys[kNumObsKeys] = {
+        {"agent", 1, as_, 0, true},
+        {"box_items", 2, B, 10, B > 0},
+        {"box_items_mask", 1, B, 0, B > 0},
+        {"box_slot", 2, 1, 8, B > 0},
+        {"box_slot_mask", 1, 1, 0, B > 0},
+        {"boxes", 2, B, 11, B > 0},
+        {"boxes_mask", 1, B, 0, B > 0},
+        {"heal_slot", 2, 1, 1, H > 0},
+        {"heal_slot_mask", 1, 1, 0, H > 0},
+        {"heals", 2, H, 2, H > 0},
+        {"heals_mask", 1, H, 0, H > 0},
+        {"lidars", 1, c.lidar_n_lasers, 0, c.lidar_n_lasers > 0},
+        {"others", 2, A - 1, as_, true},
+        {"others_mask", 1, A - 1, 0, true},
+        {"zone", 1, 6, 0, true},
     };
     int off = 0, nk = 0;
-    for (auto& k : keys) {
-        *k.off = -1;
+    for (int i = 0; i < kNumObsKeys; ++i) {
+        const K& k = keys[i];
+        off_of[i] = -1;
         if (!k.on) continue;
-        *k.off = off;
+        off_of[i] = off;
         snprintf(L.key_name[nk], 24, "%s", k.name);
         L.key_offset[nk] = off;
         L.key_ndim[nk] = k.ndim;
@@ -614,7 +622,64 @@ static void build_layout(mas_handle* h)
     }
     L.n_keys = nk;
     L.obs_dim = off;
-    P.D = off;
+}
+
+static void build_layout(mas_handle* h)
+{
+    int o[kNumObsKeys];
+    layout_of(h->cfg, h->layout, o);
+    Params& P = h->P;
+    P.o_agent = o[kAgent], P.o_bi = o[kBoxItems], P.o_bim = o[kBoxItemsMask], P.o_bs = o[kBoxSlot];
+    P.o_bsm = o[kBoxSlotMask], P.o_box = o[kBoxes], P.o_boxm = o[kBoxesMask], P.o_hs = o[kHealSlot];
+    P.o_hsm = o[kHealSlotMask], P.o_heal = o[kHeals], P.o_healm = o[kHealsMask], P.o_lid = o[kLidars];
+    P.o_oth = o[kOthers], P.o_othm = o[kOthersMask], P.o_zone = o[kZone];
+    P.D = h->layout.obs_dim;
+}
+
+// The refusals of a config that need no device: mas_create's, shared with
+// mas_bot_act.  nullptr: the config is fine.
+static const char* config_refusal(const mas_config& c)
+{
+    if (c.n_agents < 2 || c.n_heals < 0 || c.n_boxes < 0 || c.slots < 0)
+        return "n_agents must be >= 2 and counts non-negative";
+    if (c.grid_size * c.grid_size > 256 || c.n_agents + c.n_heals + c.n_boxes > c.grid_size * c.grid_size)
+        return "spawn grid too large (>256 cells) or too small for the spawns";
+    if (c.zone_phases < 1 || c.zone_n_radii + 1 > kMaxPhases || c.zone_phases > c.zone_n_radii + 1)
+        return "unsupported safe-zone phases";
+    if (c.lidar_n_lasers != 0 && (c.lidar_n_lasers < 2 || c.lidar_n_lasers > MAS_MAX_LASERS))
+        return "lidar n_lasers must be 0 or in [2, MAS_MAX_LASERS]";
+    return nullptr;
+}
+
+// The capacity class of a config: (agents, heals, boxes, slots) -- see
+// mas_k_<class>.hip; the first that fits.  false: no compiled class does.
+static bool pick_class(const mas_config& c, Ops* ops)
+{
+    auto fits = [&](int AM, int HM, int BM, int SM) {
+        return c.n_agents <= AM && c.n_heals <= HM && c.n_boxes <= BM && c.slots <= SM;
+    };
+    bool ok = false;
+    Ops o{};
+#ifdef MAS_HAVE_1v1
+    if (!ok && fits(2, 4, 4, 4)) { o = Ops{class_info_1v1(), launch_step_1v1, launch_reset_1v1, launch_view_1v1}; ok = true; }
+#endif
+#ifdef MAS_HAVE_2v2
+    if (!ok && fits(4, 4, 4, 4)) { o = Ops{class_info_2v2(), launch_step_2v2, launch_reset_2v2, launch_view_2v2}; ok = true; }
+#endif
+#ifdef MAS_HAVE_ffa
+    if (!ok && fits(4, 16, 16, 4)) { o = Ops{class_info_ffa(), launch_step_ffa, launch_reset_ffa, launch_view_ffa}; ok = true; }
+#endif
+#ifdef MAS_HAVE_ffal
+    if (!ok && fits(4, 24, 16, 8)) { o = Ops{class_info_ffal(), launch_step_ffal, launch_reset_ffal, launch_view_ffal}; ok = true; }
+#endif
+#ifdef MAS_HAVE_xl
+    if (!ok && fits(8, 8, 8, 4)) { o = Ops{class_info_xl(), launch_step_xl, launch_reset_xl, launch_view_xl}; ok = true; }
+#endif
+#ifdef MAS_HAVE_xxl
+    if (!ok && fits(8, 20, 16, 8)) { o = Ops{class_info_xxl(), launch_step_xxl, launch_reset_xxl, launch_view_xxl}; ok = true; }
+#endif
+    if (ok && ops) *ops = o;
+    return ok;
 }
 
 static int build_params(mas_handle* h)
@@ -740,14 +805,7 @@ int mas_create(const mas_config* cfg, int64_t n_envs, int32_t device, mas_handle
 {
     if (!cfg || !out || n_envs <= 0) return fail(MAS_ERR_INVALID_ARG, "mas_create: null argument or n_envs <= 0");
     const mas_config& c = *cfg;
-    if (c.n_agents < 2 || c.n_heals < 0 || c.n_boxes < 0 || c.slots < 0)
-        return fail(MAS_ERR_INVALID_ARG, "mas_create: n_agents must be >= 2 and counts non-negative");
-    if (c.grid_size * c.grid_size > 256 || c.n_agents + c.n_heals + c.n_boxes > c.grid_size * c.grid_size)
-        return fail(MAS_ERR_INVALID_ARG, "mas_create: spawn grid too large (>256 cells) or too small for the spawns");
-    if (c.zone_phases < 1 || c.zone_n_radii + 1 > kMaxPhases || c.zone_phases > c.zone_n_radii + 1)
-        return fail(MAS_ERR_INVALID_ARG, "mas_create: unsupported safe-zone phases");
-    if (c.lidar_n_lasers != 0 && (c.lidar_n_lasers < 2 || c.lidar_n_lasers > MAS_MAX_LASERS))
-        return fail(MAS_ERR_INVALID_ARG, "mas_create: lidar n_lasers must be 0 or in [2, MAS_MAX_LASERS]");
+    if (const char* why = config_refusal(c)) return fail(MAS_ERR_INVALID_ARG, std::string("mas_create: ") + why);
     // MAS_SPLIT: how mas_step uses the side streams (mas_handle::split)
     int split_mode = kSplitDefault;
     if (const char* v = getenv("MAS_SPLIT"); v && v[0]) {
@@ -762,29 +820,7 @@ int mas_create(const mas_config* cfg, int64_t n_envs, int32_t device, mas_handle
     h->cfg = c;
     h->N = n_envs;
     h->device = device;
-    auto fits = [&](int AM, int HM, int BM, int SM) {
-        return c.n_agents <= AM && c.n_heals <= HM && c.n_boxes <= BM && c.slots <= SM;
-    };
-    // capacity classes: (agents, heals, boxes, slots) -- see mas_k_<class>.hip
-    bool ok = false;
-#ifdef MAS_HAVE_1v1
-    if (!ok && fits(2, 4, 4, 4)) { h->ops = Ops{class_info_1v1(), launch_step_1v1, launch_reset_1v1, launch_view_1v1}; ok = true; }
-#endif
-#ifdef MAS_HAVE_2v2
-    if (!ok && fits(4, 4, 4, 4)) { h->ops = Ops{class_info_2v2(), launch_step_2v2, launch_reset_2v2, launch_view_2v2}; ok = true; }
-#endif
-#ifdef MAS_HAVE_ffa
-    if (!ok && fits(4, 16, 16, 4)) { h->ops = Ops{class_info_ffa(), launch_step_ffa, launch_reset_ffa, launch_view_ffa}; ok = true; }
-#endif
-#ifdef MAS_HAVE_ffal
-    if (!ok && fits(4, 24, 16, 8)) { h->ops = Ops{class_info_ffal(), launch_step_ffal, launch_reset_ffal, launch_view_ffal}; ok = true; }
-#endif
-#ifdef MAS_HAVE_xl
-    if (!ok && fits(8, 8, 8, 4)) { h->ops = Ops{class_info_xl(), launch_step_xl, launch_reset_xl, launch_view_xl}; ok = true; }
-#endif
-#ifdef MAS_HAVE_xxl
-    if (!ok && fits(8, 20, 16, 8)) { h->ops = Ops{class_info_xxl(), launch_step_xxl, launch_reset_xxl, launch_view_xxl}; ok = true; }
-#endif
+    const bool ok = pick_class(c, &h->ops);
     if (!ok) {
         delete h;
         return fail(MAS_ERR_UNSUPPORTED, "mas_create: no compiled capacity class fits this config (classes: " MAS_CLASS_LIST ")");
@@ -1441,6 +1477,40 @@ int mas_rows_select(int64_t n_envs, int32_t n_agents, uint32_t agent_mask, const
     if (n_envs == 0) return MAS_OK;
     HIP_TRY(rows_select(n_envs, n_agents, agent_mask, x_bf16, x_stride, x_out, x_out_stride, x_cols, actions,
                         actions_out, n_f32, f32_in, f32_out, (hipStream_t)stream));
+    return MAS_OK;
+}
+
+int mas_bot_act(const mas_config* cfg, int32_t kind, int64_t n_envs, uint32_t agent_mask, const void* x_bf16,
+                int64_t x_stride, int8_t* actions, void* stream)
+{
+    // every check before any HIP call
+    if (!cfg) return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: null cfg");
+    const mas_config& c = *cfg;
+    if (const char* why = config_refusal(c)) return fail(MAS_ERR_INVALID_ARG, std::string("mas_bot_act: config: ") + why);
+    if (!pick_class(c, nullptr))
+        return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: config: no compiled capacity class fits it (classes: " MAS_CLASS_LIST ")");
+    if (kind != MAS_BOT_IDLE && kind != MAS_BOT_HUNTER && kind != MAS_BOT_FORAGER)
+        return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: unknown kind (MAS_BOT_IDLE, MAS_BOT_HUNTER, MAS_BOT_FORAGER)");
+    if (c.n_agents > 32) return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: n_agents must be at most 32 (agent_mask)");
+    if (agent_mask == 0) return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: agent_mask selects no agent");
+    if (c.n_agents < 32 && (agent_mask >> c.n_agents) != 0)
+        return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: agent_mask has a bit at or above n_agents");
+    if (n_envs < 0) return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: n_envs must not be negative");
+    if (n_envs > (INT64_MAX >> 6) || bot_act_blocks(n_envs * __builtin_popcount(agent_mask)) > 0x7fffffffLL)
+        return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: n_envs too large (the block count passes 2^31)");
+    if (!x_bf16 || !actions) return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: null x_bf16 or actions");
+    mas_obs_layout L;
+    int o[kNumObsKeys];
+    layout_of(c, L, o);
+    if (!policy_act_x_ok(L.obs_dim, x_bf16, x_stride, actions))
+        return fail(MAS_ERR_INVALID_ARG, "mas_bot_act: x 16-B aligned with a padded row stride (a multiple "
+                                         "of 8 >= 16*ceil(obs_dim/16)), actions 2-B aligned");
+    if (n_envs == 0) return MAS_OK;
+    const float use_below = (float)(c.agent_health - c.healing);
+    const float reach = (float)((double)c.melee_range + c.agent_size / 2.0);
+    HIP_TRY(bot_act(kind, n_envs, c.n_agents, agent_mask, c.teams, c.n_heals, o[kAgent], o[kZone], o[kOthers],
+                    o[kOthersMask], o[kHeals], o[kHealsMask], o[kHealSlotMask], use_below, reach, x_bf16, x_stride,
+                    actions, (hipStream_t)stream));
     return MAS_OK;
 }
 

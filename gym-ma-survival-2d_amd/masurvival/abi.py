@@ -103,6 +103,8 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     'mas_rows_select': (c_int32, [c_int64, c_int32, ctypes.c_uint32, c_void_p, c_int64, c_void_p, c_int64, c_int32,
                                   c_void_p, c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), c_void_p]),
+    'mas_bot_act': (c_int32, [POINTER(MasConfig), c_int32, c_int64, ctypes.c_uint32, c_void_p, c_int64, c_void_p,
+                              c_void_p]),
     'mas_obs_stats_scratch_doubles': (c_int64, [c_int64, c_int32]),
     'mas_obs_stats': (c_int32, [c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'mas_obs_norm_merge': (c_int32, [c_int32, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
@@ -130,7 +132,7 @@ SIGNATURES = {
 OPTIONAL = {'mas_policy_train_dw3', 'mas_policy_act_sel', 'mas_rows_select', 'mas_alive', 'mas_policy_train_w',
             'mas_policy_train_dw3_w', 'mas_obs_stats_scratch_doubles', 'mas_obs_stats', 'mas_obs_norm_merge',
             'mas_policy_pack_norm', 'mas_ret_stats_scratch_doubles', 'mas_ret_stats', 'mas_gae_scaled',
-            'mas_episode_stats_scratch_doubles', 'mas_episode_stats'}
+            'mas_episode_stats_scratch_doubles', 'mas_episode_stats', 'mas_bot_act'}
 
 MAS_ERR_UNSUPPORTED = -2  # include/masurvival.h
 

@@ -11,7 +11,9 @@ and reports agent-env-steps/s.
 {'policy': state_dict} file) instead of random actions; --opponent PATH puts a
 second checkpoint on the other team; --greedy takes every head's most likely
 action instead of sampling.  With --envs N they run a masurvival.match.Match
-for --max-steps steps and print its result (wins, draws, returns).
+for --max-steps steps and print its result (wins, draws, returns).  Either
+PATH may be bot:NAME (masurvival.bots: idle, hunter, forager), a scripted
+baseline opponent instead of a checkpoint.
 
 --screenshot / --gif record `render(mode='rgb_array')` frames (device state,
 masurvival.render) as in `demo.py:178-209`, written with PIL instead of
@@ -56,9 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help='Batched mode: N device envs (auto-reset) for --max-steps steps (default 100).')
     ap.add_argument('--seed', dest='seed', type=int, default=None, help='Env seed (the reference ignores it).')
     ap.add_argument('--checkpoint', dest='checkpoint', metavar='PATH', type=str, default=None,
-                    help='Play the policy of this checkpoint instead of random actions.')
+                    help='Play the policy of this checkpoint (or the scripted bot bot:NAME) instead of random actions.')
     ap.add_argument('--opponent', dest='opponent', metavar='PATH', type=str, default=None,
-                    help='With --checkpoint: the checkpoint that plays the other team.')
+                    help='With --checkpoint: the checkpoint (or bot:NAME) that plays the other team.')
     ap.add_argument('--greedy', dest='greedy', action='store_true', default=False,
                     help='With --checkpoint: the most likely action of every head instead of a sample.')
     return ap
@@ -148,9 +150,10 @@ def demo_batched(config, n_envs: int, steps: int, seed: int = 0):
 
 
 def load_checkpoints(args, device):
-    from masurvival.match import load_policy
+    """The players of --checkpoint (and --opponent): a PolicyMLP per checkpoint path, a Bot per bot:NAME."""
+    from masurvival.match import resolve_player
     paths = [args.checkpoint] + ([args.opponent] if args.opponent is not None else [])
-    return [load_policy(p, device) for p in paths]
+    return [resolve_player(p, device) for p in paths]
 
 
 def demo_match(config, n_envs: int, steps: int, args):
@@ -174,7 +177,7 @@ def checkpoint_actions(env, args):
     from masurvival.match import Actor
     vec = env._vec
     actor = Actor(load_checkpoints(args, vec.device), 1, vec.n_agents, vec.obs_dim, vec.device, greedy=args.greedy,
-                  seed=args.seed or 0)
+                  seed=args.seed or 0, config=vec.rc)
     x = actor.x_buffer()
     out = vec._act.new_zeros(vec._act.shape)
 

@@ -11,6 +11,13 @@ own agents' rows through ``mas_policy_act_sel`` (include/masurvival.h): the
 policies' masks are disjoint, so they fill disjoint rows of one actions buffer
 and share the RNG key ``(seed, t)``.  On the CPU (a scripted env double) the
 torch fp32 forward and ``sample_actions`` stand in.
+
+Either side may be a scripted bot (``masurvival.bots``: a ``Bot`` or a
+``'bot:NAME'`` string) instead of a policy: a fixed yardstick that does not
+move between runs.  On a GPU its rows are filled by ``mas_bot_act`` with the
+mask ``act_sel`` would get, on the CPU by ``bot_actions_reference``; a bot draws
+no random numbers, and the policies' rows and RNG keys are what they are
+without it.
 """
 from __future__ import annotations
 
@@ -19,6 +26,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from .bots import Bot, bot_act, bot_actions_reference, is_bot_spec, parse_bot
 from .ppo import HEADS, FusedPolicy, ObsNorm, PolicyMLP, sample_actions
 
 _COUNT_EVERY = 32  # run(episodes=...) reads the device's episode count every this many steps
@@ -42,6 +50,19 @@ def load_policy(src, device='cpu') -> PolicyMLP:
     return policy.to(device).eval()
 
 
+def resolve_player(p, device='cpu'):
+    """One entry of a `policies` list as Match takes them: a PolicyMLP (as it
+    is), a bot (a Bot or a 'bot:NAME' string -> Bot), or a checkpoint (a path
+    or a loaded dict -> load_policy)."""
+    if isinstance(p, (PolicyMLP, Bot)):
+        return p
+    if is_bot_spec(p):
+        return parse_bot(p)
+    if isinstance(p, (str, bytes, os.PathLike, dict)):
+        return load_policy(p, device)
+    return p
+
+
 def greedy_actions(raw):
     """Per-head arg-max (the first index wins a tie) of raw [.., 16] head
     outputs; int8 [.., 6]."""
@@ -63,14 +84,27 @@ class Actor:
     [n_envs // 2, n_envs) use the inverted assignment.  ``act(src, t, out)``
     fills out int8 [n_envs, n_agents, 6]: on a GPU `src` is the bf16 row buffer
     [n_envs * n_agents, Dx] (``x_buffer``), on the CPU the fp32 obs
-    [n_envs, n_agents, obs_dim]."""
+    [n_envs, n_agents, obs_dim].
+
+    A side may be a bot (a Bot or 'bot:NAME'); then `config` (the env's
+    ResolvedConfig, or its mas_config struct) is needed: the rule reads the
+    row's layout and its thresholds from it."""
 
     def __init__(self, policies, n_envs, n_agents, obs_dim, device, assignment=None, greedy=False, seed=0,
-                 swap_sides=False):
-        policies = list(policies)
+                 swap_sides=False, config=None):
+        policies = [resolve_player(p, device) for p in policies]
         if len(policies) not in (1, 2):
             raise ValueError(f'need one or two policies, got {len(policies)}')
+        self.cfg_struct = None
+        if any(isinstance(p, Bot) for p in policies):
+            if config is None:
+                raise ValueError('a bot needs the env config (config=, or an env with .rc)')
+            self.cfg_struct = config.to_struct() if hasattr(config, 'to_struct') else config
+            if int(self.cfg_struct.n_agents) != int(n_agents):
+                raise ValueError(f'config n_agents {int(self.cfg_struct.n_agents)} does not match n_agents {n_agents}')
         for p in policies:
+            if isinstance(p, Bot):
+                continue
             d = p.body[0].weight.shape[1]
             if d != obs_dim:
                 raise ValueError(f'policy obs_dim {d} does not match the env obs_dim {obs_dim}')
@@ -99,9 +133,10 @@ class Actor:
         self.policies = [policies[min(s, len(policies) - 1)] for s in (0, 1)]
         self.fused = None
         if self.device.type == 'cuda':
-            fps = [FusedPolicy(p, self.D, self.device) for p in policies]
+            fps = [None if isinstance(p, Bot) else FusedPolicy(p, self.D, self.device) for p in policies]
             for fp in fps:
-                fp.pack()
+                if fp is not None:
+                    fp.pack()
             self.fused = [fps[min(s, len(fps) - 1)] for s in (0, 1)]
             M = self.N * self.A
             self.logp = torch.empty((M,), dtype=torch.float32, device=self.device)
@@ -111,7 +146,13 @@ class Actor:
             self.gen.manual_seed(self.seed)
 
     def x_buffer(self):
-        return self.fused[0].x_buffer(self.N * self.A)
+        """bf16 rows [n_envs * n_agents, Dx] as FusedPolicy.x_buffer lays them
+        out (the bias column at index D = 1); made here, since a side may be a
+        bot and have no FusedPolicy."""
+        Dx = 16 * ((self.D + 1 + 15) // 16)
+        x = torch.zeros((self.N * self.A, Dx), dtype=torch.bfloat16, device=self.device)
+        x[..., self.D] = 1.0
+        return x
 
     @torch.no_grad()
     def act(self, src, t, out):
@@ -124,12 +165,19 @@ class Actor:
                     mask = _mask_of(sides, s)
                     if mask == 0 or r1 == r0:
                         continue  # this side has no agent in the slice: its policy is not called
+                    if isinstance(self.policies[s], Bot):
+                        bot_act(self.cfg_struct, self.policies[s], src[r0:r1], A, mask, acts[r0:r1])
+                        continue
                     self.fused[s].act_sel(src[r0:r1], A, mask, self.seed, t, acts[r0:r1], self.logp[r0:r1],
                                           self.value[r0:r1], greedy=self.greedy, first_row=r0)
             return out
         for s in (0, 1):
             sel = self.side if s == 1 else ~self.side
             if not bool(sel.any()):
+                continue
+            if isinstance(self.policies[s], Bot):
+                a = bot_actions_reference(self.policies[s], src, self.cfg_struct).to(out.device)
+                out.copy_(torch.where(sel.unsqueeze(-1), a, out))
                 continue
             raw = self.policies[s].forward_raw(src.float())
             a = greedy_actions(raw) if self.greedy else sample_actions(raw[..., :sum(HEADS)], self.gen)[0]
@@ -140,6 +188,8 @@ class Actor:
 class Match:
     """One or two policies in `env` (a VecMaSurvival, or anything with its
     reset / step / n_envs / n_agents / obs_dim / device / auto_reset surface).
+    Each may be a PolicyMLP, a checkpoint (path or loaded dict) or a bot (a Bot
+    or 'bot:NAME'; the env then needs its ResolvedConfig as `.rc`).
 
     The act RNG key is (seed, t), t counting this match's steps from 0.
     ``step()`` advances every env one step and returns (rewards [N, A], dones
@@ -151,14 +201,15 @@ class Match:
                  seed: int = 0, swap_sides: bool = False):
         if not getattr(env, 'auto_reset', False):
             raise ValueError('Match needs an auto-resetting env (auto_reset=True)')
-        policies = list(policies)
-        dims = [int(p.body[0].weight.shape[1]) for p in policies]
+        policies = [resolve_player(p, env.device) for p in policies]
+        dims = [int(p.body[0].weight.shape[1]) for p in policies if not isinstance(p, Bot)]
         if any(d != env.obs_dim for d in dims):
             raise ValueError(f'policy obs_dim {dims} does not match the env obs_dim {env.obs_dim}')
         self.env = env
         N, A = int(env.n_envs), int(env.n_agents)
         dev = torch.device(env.device)
-        self.actor = Actor(policies, N, A, env.obs_dim, dev, assignment, greedy, seed, swap_sides)
+        self.actor = Actor(policies, N, A, env.obs_dim, dev, assignment, greedy, seed, swap_sides,
+                           config=getattr(env, 'rc', None))
         self.on_gpu = dev.type == 'cuda'
         self.use_step_x = bool(self.on_gpu and hasattr(env, 'step_x') and env.supports_step_x())
         self.actions = torch.zeros((N, A, 6), dtype=torch.int8, device=dev)

@@ -1544,10 +1544,24 @@ class PPOTrainer:
         the agents outside `learner_agents`; the trained policy acts for and is
         updated on the rows of `learner_agents` only (default with an
         opponent: range(n_agents // 2), Match's side 0).  Both None: every
-        agent is the trained policy's and nothing below changes."""
+        agent is the trained policy's and nothing below changes.
+        opponent may also be a scripted bot (masurvival.bots: a Bot or a
+        'bot:NAME' string): it fills the other agents' action rows by its fixed
+        rule (mas_bot_act on a GPU); it is kept as `opponent_bot`, `opponent`
+        stays None, and there is nothing to sync."""
+        from .bots import is_bot_spec, parse_bot
         self.env, self.cfg = env, cfg
         self.device = env.device
-        self.opponent, self.learner_agents = self._resolve_selfplay(env, opponent, learner_agents)
+        self.opponent_bot = parse_bot(opponent) if is_bot_spec(opponent) else None
+        if self.opponent_bot is not None:
+            if int(cfg.opponent_sync_every) > 0:
+                raise ValueError('opponent_sync_every > 0 needs a policy opponent: a bot has no weights to sync')
+            if getattr(env, 'rc', None) is None:
+                raise ValueError('a bot opponent needs the env config (an env with .rc)')
+            self._bot_cfg = env.rc.to_struct()
+            opponent = None
+        self.opponent, self.learner_agents = self._resolve_selfplay(env, opponent, learner_agents,
+                                                                    self.opponent_bot is not None)
         self.group = group
         self.world = dist.get_world_size(group) if group is not None or dist.is_initialized() else 1
         self.collectives = self.world > 1 if cfg.allreduce is None else bool(cfg.allreduce)
@@ -1633,11 +1647,14 @@ class PPOTrainer:
         A = self.env.n_agents if self.learner_agents is None else len(self.learner_agents)
         return int(self.env.n_envs) * int(A)
 
+    def _has_opponent(self):
+        return self.opponent is not None or self.opponent_bot is not None
+
     def _side0_mask(self):
         """Side 0 of the episode statistics: the learner's agents against an
         opponent, otherwise agents range(A // 2) (Match's side 0; none for one agent)."""
         A = int(self.env.n_agents)
-        side0 = self.learner_agents if self.opponent is not None else range(A // 2)
+        side0 = self.learner_agents if self._has_opponent() else range(A // 2)
         return _agent_mask(side0, A, 'side 0') if len(side0) else 0
 
     def _episode_last_stats(self):
@@ -1693,10 +1710,11 @@ class PPOTrainer:
             self._obs_norm_update(b.obs[:T].reshape(-1, b.D).to(torch.bfloat16), kernel=False)
 
     @staticmethod
-    def _resolve_selfplay(env, opponent, learner_agents):
+    def _resolve_selfplay(env, opponent, learner_agents, bot=False):
         """(frozen opponent PolicyMLP or None, sorted learner agent list or
-        None) from the constructor's arguments, or ValueError."""
-        if opponent is None and learner_agents is None:
+        None) from the constructor's arguments, or ValueError.  bot: a scripted
+        bot stands where the opponent would (opponent is None then)."""
+        if opponent is None and learner_agents is None and not bot:
             return None, None
         A = int(env.n_agents)
         if not 1 <= A <= 32:
@@ -1706,6 +1724,10 @@ class PPOTrainer:
         learner_agents = [int(a) for a in learner_agents]
         _agent_mask(learner_agents, A, 'learner_agents')
         whole = len(learner_agents) == A
+        if bot:
+            if whole:
+                raise ValueError('learner_agents must be a proper subset of the agents when an opponent is given')
+            return None, sorted(learner_agents)
         if opponent is None:
             if not whole:
                 raise ValueError(f'learner_agents {learner_agents} leaves agents without a policy: give an opponent')
@@ -1745,6 +1767,8 @@ class PPOTrainer:
                 raise ValueError(f'self-play on a GPU needs {why}')
             if not hasattr(self.fused.lib, 'mas_rows_select') or not hasattr(self.fused.lib, 'mas_policy_act_sel'):
                 raise MasError('the loaded library has no mas_rows_select / mas_policy_act_sel')
+            if self.opponent_bot is not None and not hasattr(self.fused.lib, 'mas_bot_act'):
+                raise MasError('the loaded library has no mas_bot_act')
             if self.opponent is not None:
                 self.opp_fused = FusedPolicy(self.opponent, self.env.obs_dim, self.device)
                 self.opp_fused.pack()
@@ -1759,6 +1783,8 @@ class PPOTrainer:
     def sync_opponent(self):
         """Lagged self-play: the opponent becomes a copy of the learner's
         current fp32 weights (and is packed again for the kernels)."""
+        if self.opponent_bot is not None:
+            raise ValueError(f'sync_opponent: the opponent is the bot {self.opponent_bot.name!r}, which has no weights')
         if self.opponent is None:
             raise ValueError('sync_opponent: this trainer has no opponent')
         for d, s_ in zip(self.opponent.parameters(), self.policy.parameters()):
@@ -1808,6 +1834,9 @@ class PPOTrainer:
                                b.values[t].view(-1))
             if self.opp_fused is not None:
                 self.opp_fused.act_sel(b.xb[t], b.A, self._omask, self.seed, self.steps_taken, acts, *self._opp_out)
+            elif self.opponent_bot is not None:
+                from .bots import bot_act
+                bot_act(self._bot_cfg, self.opponent_bot, b.xb[t], b.A, self._omask, acts)
             self.steps_taken += 1
             self.env.step_x(b.actions[t], b.xb[t + 1], b.rewards[t], b.dones[t])
             return
@@ -1816,6 +1845,10 @@ class PPOTrainer:
         if self.opponent is not None:
             ao, _ = sample_actions(self._fwd(b.obs[t], self.opponent)[0], self.gen)
             a = torch.where(self._lsel.view(1, -1, 1), a, ao)
+        elif self.opponent_bot is not None:
+            from .bots import bot_actions_reference
+            ao = bot_actions_reference(self.opponent_bot, b.obs[t], self._bot_cfg)
+            a = torch.where(self._lsel.view(1, -1, 1), a, ao.to(a.dtype))
         b.actions[t].copy_(a)
         b.logp[t].copy_(lp)
         b.values[t].copy_(v)
@@ -2078,6 +2111,8 @@ class PPOTrainer:
             # self-play: 'policy' stays the learner (match.load_policy reads it as any checkpoint's)
             sd['learner_agents'] = [int(a) for a in self.learner_agents]
             sd['iterations'] = int(self.iterations)
+            if self.opponent_bot is not None:
+                sd['opponent_bot'] = self.opponent_bot.name
             if self.opponent is not None:
                 sd['opponent'] = {k: v.detach().clone() for k, v in self.opponent.state_dict().items()}
                 if self.opponent.obs_mean is not None:  # the frozen normaliser as the opponent applies it
@@ -2097,6 +2132,9 @@ class PPOTrainer:
         have = sd.get('learner_agents')
         if (None if have is None else [int(a) for a in have]) != self.learner_agents:
             raise ValueError(f'checkpoint learner_agents {have} differ from this trainer\'s {self.learner_agents}')
+        have_bot, my_bot = sd.get('opponent_bot'), (None if self.opponent_bot is None else self.opponent_bot.name)
+        if have_bot != my_bot:
+            raise ValueError(f'checkpoint opponent bot {have_bot!r} differs from this trainer\'s {my_bot!r}')
         if ('opponent' in sd) != (self.opponent is not None):
             raise ValueError('checkpoint and trainer disagree on having an opponent')
         if self.opponent is not None:

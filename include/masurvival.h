@@ -447,6 +447,69 @@ int mas_rows_select(int64_t n_envs, int32_t n_agents, uint32_t agent_mask,
                     const int8_t* actions, int8_t* actions_out, /* [rows][6] */
                     int32_t n_f32, const float* const* f32_in, float* const* f32_out,
                     void* stream);
+/* mas_bot_act (an addition within ABI version 3): scripted baseline opponents
+ * on the device.  Fills the action rows of the bit-selected agents of n_envs
+ * whole envs from their bf16 observation rows, by a fixed rule: the slot of
+ * mas_policy_act_sel with no network.  Rows and mask are addressed as there
+ * (row = env * n_agents + agent with n_agents = cfg->n_agents; bit a of
+ * agent_mask selects agent a of every env); only the selected rows are read,
+ * columns at or past the config's obs_dim never, and only their 6 action bytes
+ * are written.  x_bf16 [rows][x_stride]: 16-B aligned, x_stride a multiple of
+ * 8 >= 16*ceil(obs_dim/16) (mas_policy_act_sel's rules); actions 2-B aligned.
+ * The column offsets (mas_get_obs_layout's) and the thresholds come from cfg on
+ * the host at every call: no handle, so the call serves any row buffer of that
+ * config.  Stream-ordered, allocates nothing, never synchronises, capturable;
+ * no random numbers: the same row bits give the same action bytes.
+ *
+ * The rule.  A bf16 value is exact in fp32, so the inputs are exact.  All
+ * arithmetic is fp32, every operation rounded on its own (no fma), IEEE divide
+ * and sqrt; x^2 means x * x; the decimal constants below are their nearest
+ * fp32.  From the row (an agent record is [id, (team when cfg->teams), health,
+ * x, y, angle, vx, vy, w]):
+ *   self: health, pos = (x, y), theta = angle, w (angular velocity), team
+ *   zone: zone_c = zone[0..1], zone_r = zone[2]
+ *   others[j], others_mask[j]  j < n_agents - 1;  heals[k] = (x, y),
+ *   heals_mask[k]  k < n_heals;  heal_slot_mask          (when n_heals > 0)
+ * Actions a[0..5] (MultiDiscrete [3,3,3,2,2,2]; 1 is "nothing" in a[0..2]):
+ *   kind IDLE, or health <= 0:  a = [1,1,1,0,0,0], and nothing below applies.
+ *   a[1] = 1, a[5] = 0.
+ *   a[4] = 1 exactly when n_heals > 0 and heal_slot_mask == 0 and
+ *          health <= agent_health - healing (an integer, exact in fp32).
+ * Target, the first that applies:
+ *   1. e = pos - zone_c, m = max(zone_r - 1, 0):  |e|^2 > m^2  (|e|^2 =
+ *      e.x^2 + e.y^2): the zone centre.
+ *   2. FORAGER with n_heals > 0: the heal k with heals_mask[k] == 0 and not
+ *      |heals[k] - zone_c|^2 > m^2 (a heal outside the zone's margin is left
+ *      alone) of the least |heals[k] - pos|^2, if there is one.
+ *   3. the other agent j with others_mask[j] == 0, health_j > 0 and, when
+ *      cfg->teams, team_j != team, of the least |pos_j - pos|^2, if there is
+ *      one; FORAGER takes it unless that least value is > 4^2 (only within 4 m).
+ *   Among equal squared distances the lowest index (k or j) wins.
+ *   4. no target: a = [1, 1, 2, 0, a[4], 0] (turn counter-clockwise in place).
+ * Steering towards target t:  d = t - pos, l = sqrt(d.x^2 + d.y^2),
+ *   h = ((float)cos, (float)sin) of (double)theta from the library's shared
+ *   double sincos (Cody-Waite reduction, fdlibm kernels), c = h.x d.x + h.y d.y,
+ *   s = h.x d.y - h.y d.x,  u = s - (0.25 w) l   (the turn leads its own
+ *   angular velocity by 0.25 s: the bang-bang turn alone overshoots),
+ *   b = 0.15 l:
+ *   a[2] = 2 if u > b; else 0 if -b > u; else 2 if 0 > c; else 1.
+ *   a[0] = 2 if c > 0.8 l and l > stop, stop = 1.25 for an enemy (3.) and
+ *          0.25 for the zone centre or a heal (it has arrived); else 1.
+ *   a[3] = 1 if the target is an enemy, not l > reach and c > 0.9 l, where
+ *          reach = (float)(melee_range + agent_size / 2) formed in double;
+ *          else 0.
+ *
+ * MAS_ERR_INVALID_ARG, before any device work: a null cfg or a config
+ * mas_create refuses (one that no compiled capacity class fits included), an
+ * unknown kind, a zero agent_mask or a mask bit at or
+ * above n_agents (or n_agents > 32), n_envs < 0 or so many selected rows that
+ * the block count passes 2^31, a null x_bf16 or actions, a bad stride or
+ * alignment.  n_envs == 0 is MAS_OK and launches nothing. */
+#define MAS_BOT_IDLE 0
+#define MAS_BOT_HUNTER 1
+#define MAS_BOT_FORAGER 2
+int mas_bot_act(const mas_config* cfg, int32_t kind, int64_t n_envs, uint32_t agent_mask,
+                const void* x_bf16, int64_t x_stride, int8_t* actions, void* stream);
 /* Running observation normalisation (additions within ABI version 3).  The
  * normaliser (per-column mean and 1 / std) is never applied to a row: it is
  * folded into the packed layer-1 weights, W1 ((x - mean) * s) + b1 =
