@@ -863,6 +863,7 @@ int mas_create(const mas_config* cfg, int64_t n_envs, int32_t device, mas_handle
         h->P.slow_k = k ? atoi(k) : 4;  // TOI events of an env's step that make it slow (the cap always does)
     }
     h->P.list_overflow = h->phys ? h->phys + list_ints + 3 : nullptr;
+    h->P.spawn_refused = h->phys ? h->phys + list_ints + 4 : nullptr;
     h->slow = nullptr;
     h->slow_flag = nullptr;
     if (e == hipSuccess) e = hipMalloc(&h->slow, ((size_t)n_envs + 4) * sizeof(int));
@@ -1302,6 +1303,16 @@ int mas_debug_guards(mas_handle* h, int64_t* host_out)
     int c = 0;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(&c, h->P.list_overflow, sizeof(int), hipMemcpyDeviceToHost));
+    host_out[0] = c;
+    return MAS_OK;
+}
+
+int mas_debug_spawn_refused(mas_handle* h, int64_t* host_out)
+{
+    if (!h || !host_out) return fail(MAS_ERR_INVALID_ARG, "mas_debug_spawn_refused: null argument");
+    int c = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(&c, h->P.spawn_refused, sizeof(int), hipMemcpyDeviceToHost));
     host_out[0] = c;
     return MAS_OK;
 }

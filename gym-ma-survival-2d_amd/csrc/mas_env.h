@@ -94,6 +94,7 @@ struct Params {
     int list_shards, list_cap;
     int* phys_last;   // the last step's count, copied there before the zeroing (mas_debug_counters)
     int* list_overflow;  // appends to phys_list / slow_list / reset_list refused by their bounds (mas_debug_guards)
+    int* spawn_refused;  // boxes, box items and heals not spawned because the config's n_boxes / n_heals were there (mas_debug_spawn_refused)
     int* reset_list;     // [N] the done envs of this step's post kernel (auto-reset; the side stream: its own list)
     int* reset_count;    // their count: zeroed by k_pre, appended by k_post_lanes, read by the reset launch
     int reset_in_post;   // the auto-reset runs inside k_post_lanes (no reset list, no reset launch)

@@ -536,18 +536,20 @@ __global__ __launch_bounds__(kWG, MAS_PRE_OCC) void k_pre_lanes(Params P, uint32
     // ---------------- pre_step ----------------
     // boxes: Object.pre_step drops last step's queued box items
     // (semantics.py:853-856): appended to the box items in queue order, up to
-    // the capacity (spawn_bitem)
+    // the config's n_boxes, the slots a row has (spawn_bitem)
     const int npend = (int)V.pw(0), nbi0 = V.nbi();
     if (npend > 0) dirty |= kGItem | kGPend;
     for (int k = i; k < C::BM; k += AM) {
-        if (k < npend && nbi0 + k < C::BM) {
+        if (k < npend && nbi0 + k < P.B) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) V.iw(1 + 5 * (nbi0 + k) + q) = V.pw(1 + 5 * k + q);
+        } else if (k < npend) {
+            atomicAdd(P.spawn_refused, 1);
         }
     }
     wave_lds_sync();
     if (i == 0) {
-        V.iw(0) = (uint32_t)(nbi0 + npend < C::BM ? nbi0 + npend : C::BM);
+        V.iw(0) = (uint32_t)(nbi0 + npend < P.B ? nbi0 + npend : P.B);
         V.pw(0) = 0u;
     }
     // agents: DynamicMotors (simulation.py:407-424).  qs / qc: the agent's
@@ -591,7 +593,9 @@ __global__ __launch_bounds__(kWG, MAS_PRE_OCC) void k_pre_lanes(Params P, uint32
     if (use_box) {
         // spawn_box: the agent's rank among this step's box users
         const int b = nbox0 + __popc(boxers & ((1u << i) - 1u));
-        if (b < C::BM) {
+        if (b >= P.B) {
+            atomicAdd(P.spawn_refused, 1);  // the item is used up, no box appears
+        } else {
             const V2 off = from_polar(P.box_item_offset, g.a);
             const V2 pos = add(g.c, off);
             V.bw(1 + 6 * b) = __float_as_uint(pos.x);
@@ -605,7 +609,7 @@ __global__ __launch_bounds__(kWG, MAS_PRE_OCC) void k_pre_lanes(Params P, uint32
     }
     if (i == 0 && boxers) {
         const int nb = nbox0 + __popc(boxers);
-        V.bw(0) = (uint32_t)(nb < C::BM ? nb : C::BM);
+        V.bw(0) = (uint32_t)(nb < P.B ? nb : P.B);
     }
     wave_lds_sync();
     // GiveLast (semantics.py:335-370): nearest body centre within the give

@@ -1074,14 +1074,18 @@ __global__ MAS_POST_BOUNDS void k_post_lanes(Params P_, uint32_t* __restrict__ s
                     const int meta = (int)dref(3 + 3 * q, k);
                     if (it_kind(meta) == kItemHeal) {
                         const int nh = V.nheal();
-                        if (nh < C::HM) {
+                        if (nh < P.H) {
                             V.hw(1 + 2 * nh) = __float_as_uint(pos.x);
                             V.hw(2 + 2 * nh) = __float_as_uint(pos.y);
                             V.hw(0) = (uint32_t)(nh + 1);
+                        } else {
+                            atomicAdd(P.spawn_refused, 1);
                         }
                     } else {
                         const int ni = V.nbi();
-                        if (ni < C::BM) {
+                        if (ni >= P.B) {
+                            atomicAdd(P.spawn_refused, 1);
+                        } else {
                             V.iw(1 + 5 * ni) = __float_as_uint(pos.x);
                             V.iw(2 + 5 * ni) = __float_as_uint(pos.y);
                             V.iw(3 + 5 * ni) = dref(4 + 3 * q, k);

@@ -82,6 +82,7 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p]),
     'mas_debug_counters': (c_int32, [c_void_p, POINTER(c_int64)]),
     'mas_debug_guards': (c_int32, [c_void_p, POINTER(c_int64)]),
+    'mas_debug_spawn_refused': (c_int32, [c_void_p, POINTER(c_int64)]),
     'mas_debug_force_general': (c_int32, [c_void_p, c_int32]),
     'mas_invalid_actions': (c_int32, [c_void_p, POINTER(c_int64), c_int32]),
     'mas_debug_gen_flags': (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -217,6 +217,13 @@ class VecMaSurvival:
         check(self._lib.mas_debug_guards(self._h, out))
         return {'list_overflow': int(out[0])}
 
+    def spawn_refused(self) -> int:
+        """Boxes, box items and heals not spawned since creation because the
+        env already held n_boxes / n_heals of them; synchronises."""
+        out = (ctypes.c_int64 * 1)()
+        check(self._lib.mas_debug_spawn_refused(self._h, out))
+        return int(out[0])
+
     def force_general(self, on: bool = True):
         """Test diagnostics: every env takes the general physics path (on)."""
         bits = getattr(self, '_dbg_bits', 0) & 12

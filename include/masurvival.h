@@ -677,6 +677,12 @@ int mas_debug_counters(mas_handle* h, int64_t* host_out);
  * so this is 0 unless a kernel breaks that invariant; the tests assert it. */
 int mas_debug_guards(mas_handle* h, int64_t* host_out);
 
+/* Diagnostics (synchronises the device): host_out[0] = boxes, box items and
+ * heals that were not spawned since mas_create because the env already held
+ * the config's n_boxes / n_heals of them, the slots an observation row has.
+ * Only the copies of double pickups make more items than a reset deals. */
+int mas_debug_spawn_refused(mas_handle* h, int64_t* host_out);
+
 /* Test diagnostics: bit 0 of `on` sends every env of every following
  * mas_step through the general physics path (the contact-free fast path
  * gives up for all envs); bit 1 (the former one-lane-per-env general

@@ -1532,8 +1532,16 @@ static void sync_statics(ora_env* e)
 }
 
 /* Group.spawn for boxes (simulation.py:178-183): appended, new contacts */
+/* An env holds at most the config's n_boxes boxes, n_boxes box items and
+ * n_heals heals, the slots an observation row has: a spawn beyond that is
+ * refused (the used or dropped item is gone).  Only the copies of double
+ * pickups make more items than a reset deals, and the reference's observation
+ * code has no room for them. */
+int64_t g_spawn_refused = 0;
+
 static void spawn_box(ora_env* e, v2 pos, const poly* shape, int vuln)
 {
+    if (e->nbox >= e->B) { g_spawn_refused++; return; }
     box_t* b = &e->box[e->nbox];
     b->serial = e->next_serial++;
     b->pos = pos;
@@ -1565,7 +1573,7 @@ static void despawn_box(ora_env* e, int idx)
 
 static void spawn_heal(ora_env* e, v2 pos)
 {
-    if (e->nheal >= OH) return;
+    if (e->nheal >= e->H) { g_spawn_refused++; return; }
     e->heal[e->nheal].serial = e->next_serial++;
     e->heal[e->nheal].pos = pos;
     e->nheal++;
@@ -1573,7 +1581,7 @@ static void spawn_heal(ora_env* e, v2 pos)
 
 static void spawn_bitem(ora_env* e, v2 pos, const poly* shape, int owner)
 {
-    if (e->nbi >= OB) return;
+    if (e->nbi >= e->B) { g_spawn_refused++; return; }
     bitem_t* b = &e->bi[e->nbi++];
     b->serial = e->next_serial++;
     b->pos = pos;

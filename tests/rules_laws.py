@@ -198,6 +198,7 @@ def law_ledger(C, prev, new, actions, valid, L, st, t):
     hit_any = T.kind != rr.NONE
     sure = pressed & hit_any & ~graze & (L.cd_hi == 0)
     maybe = pressed & (hit_any | graze) & (L.cd_lo == 0) & ~sure
+    swings = SimpleNamespace(T=T, sure=sure, maybe=maybe.copy(), graze=graze, ready=L.cd_hi == 0)   # for items_laws (law K)
     at_agent = (T.kind == rr.AGENT)[:, :, None] & (T.idx[:, :, None] == np.arange(A)[None, None, :])   # [N, i, j]
     foe = prev.team[:, :, None] != prev.team[:, None, :]
     hits = (sure[:, :, None] & at_agent & foe).sum(1)
@@ -267,7 +268,8 @@ def law_ledger(C, prev, new, actions, valid, L, st, t):
                     maybe[n, i] = False
                 else:
                     st.add('ledger_wrong', 1)
-            elif T.kind[n, i] == rr.BOX and C.damage >= C.box_health and not box_sure[n, j]:
+            elif T.kind[n, i] == rr.BOX and C.damage >= C.box_health and not box_sure[n, j] and not C.rc.box_ownership:
+                # (an owned box stays when anybody but its owner hits it: it shows nothing about the cooldown)
                 if (maybe[n, :] & ~graze[n, :] & (T.kind[n, :] == rr.BOX) & (T.idx[n, :] == j)).sum() == 1:
                     if gone[n, j]:
                         fired[n, i] = True
@@ -279,7 +281,8 @@ def law_ledger(C, prev, new, actions, valid, L, st, t):
         L.cd_lo = np.where(fired, C.cooldown, np.where(open_, np.where(~graze & hit_any, np.minimum(np.maximum(L.cd_lo, 1), C.cooldown), 0), L.cd_lo))
         L.cd_hi = np.where(fired | open_, C.cooldown, L.cd_hi)
         L.cd_lo, L.cd_hi = np.maximum(L.cd_lo - 1, 0), np.maximum(L.cd_hi - 1, 0)
-    return SimpleNamespace(blind=placed | due, due_pos=due_pos, used_any=alive0 & (a[..., 4] == 1), gave=alive0 & (a[..., 5] == 1))
+    return SimpleNamespace(blind=placed | due, due_pos=due_pos, used_any=alive0 & (a[..., 4] == 1), gave=alive0 & (a[..., 5] == 1),
+                           swings=swings)
 
 
 def _near_rim(new, prev):
@@ -315,8 +318,8 @@ def law_pickup(C, prev, new, valid, led, L, st, t):
     is in doubt: an item within BAND of the radius, a `give` pressed anywhere in
     the env, an agent dying within reach (its items drop around it), or a box
     item due from a box broken the step before (law C's `blind` steps, for
-    agents near the spot).  `give` and DeathDrop placement themselves are not
-    judged."""
+    agents near the spot).  `give`, placing and DeathDrop themselves are
+    judged by tests/items_laws.py, which keeps every stack item by item."""
     N, A = prev.N, C.A
     alive1 = new.present
     # uses come first
